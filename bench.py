@@ -12,7 +12,12 @@ Launch forms:
   python bench.py --gpus N                         this process only spawns N fresh children (one rank per GPU) BEFORE
                                                    touching the GPU, waits for them and exits with their status
 
-Prints ONE JSON line on rank 0 (see the contract in the round prompt): value = decoded info Mbit/s over all GPUs.
+Prints ONE JSON line on rank 0: value = decoded info Mbit/s over all GPUs, ms_per_step = wall clock of one timed step.
+
+A plain run does only what that line needs: set-up, --warmup steps, the --steps timed steps, the outputs of the last step
+(--dump-outputs DIR) and the line.  --full adds everything else the benchmark measures or checks: the shader-clock probes,
+the sustained leg, the in-run parity check against the scalar reference, the CPU baseline and, behind the default workload,
+the other BASELINE configs in the same line (`configs: [...]`).
 """
 import argparse
 import json
@@ -98,7 +103,18 @@ def parse():
     ap.add_argument("--parity", action="store_true", help="run the in-run parity check against the scalar reference even with --no-cpu-baseline")
     ap.add_argument("--synth", default="hip", choices=["hip", "torch"],
                     help="frame synthesis (untimed): hip = vit_hip_synth_batch (one HIP kernel), torch = ATen elementwise ops")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: shader-clock probes, the sustained leg, parity against the scalar reference, the CPU "
+                         "baseline and (default workload, N = 1) the other BASELINE configs.  Without it a run only sets up, warms "
+                         "up, times the --steps steps, dumps outputs if asked and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the last timed step computed (the decoded bytes) as DIR/<name>.npy, "
+                         "float32; a fixed, seeded sample of the frames where the whole batch would exceed 32 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.config is not None:
         code, dt, frames, bits, ebn0 = BASELINE_CONFIGS[args.config]
         args.code, args.decode_type, args.frames, args.bits, args.ebn0 = code, dt, frames, bits, ebn0
@@ -336,6 +352,24 @@ def reference_parity(code_id, code, pc, decode_type, last_decisions, sym_dev, ou
             "chainback_bytes_bit_exact": bool(ok_b), "decision_words_bit_exact": bool(ok_d), "bit_exact": bool(ok_b and ok_d)}
 
 
+DUMP_MAX_BYTES = 32 << 20
+
+
+def dump_outputs(out_dir, decoded, prefix=""):
+    """--dump-outputs: the decoded bytes [F][L/8] of the last timed step as float32 (every value exact).  Where the whole batch
+    would exceed DUMP_MAX_BYTES, a fixed sample of frames (seed 0, sorted) -- the same rows on every run with the same arguments;
+    their indices go beside them."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    F, nb = int(decoded.shape[0]), int(decoded.shape[1])
+    n = max(1, min(F, DUMP_MAX_BYTES // (4 * max(nb, 1))))
+    idx = np.arange(F) if n == F else np.sort(np.random.default_rng(0).choice(F, n, replace=False))
+    rows = decoded[idx].cpu().numpy() if hasattr(decoded, "cpu") else np.asarray(decoded)[idx]
+    np.save(os.path.join(out_dir, f"{prefix}decoded_bytes.npy"), rows.astype(np.float32))
+    np.save(os.path.join(out_dir, f"{prefix}decoded_frame_index.npy"), idx.astype(np.float64))
+
+
 def run_case(cfg_index, steps, warmup, local_rank, dev, sustain_seconds=1.0):
     """One more BASELINE config after the headline, through the same shipped pipeline API (vit_hip_pipeline_submit per step): its own
     decoder, synthetic batch and workspaces, freed before the next one.  Returns the compact record that goes into `configs: [...]`:
@@ -555,7 +589,25 @@ def host_route_result(args):
         acc, out = one()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, out.reshape(1, -1))
     S = L + code.K - 1
+    step_ms = elapsed / args.steps * 1e3
+    full = getattr(args, "full", True)
+    if not full:
+        # a plain run: the headline figures of the timed steps only (no checker, no CPU leg)
+        return {
+            "metric": "decoded Mbit/s (= ACS trellis steps/s), update()+chainback(), bit-exact vs scalar reference",
+            "value": L * args.steps / elapsed / 1e6, "unit": "Mbit/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": step_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u16" if pc.error_bytes == 2 else "u8", "data": "synthetic",
+            "config": {"workload": f"{code.name} K={code.K} R=1/{code.R} {args.decode_type}, ONE frame of {L} info bits through the header-level drop-in "
+                                   f"(ViterbiDecoder_HIP::update + ViterbiDecoder_Core::chainback, host-resident state), AWGN Eb/N0={args.ebn0} dB",
+                       "frames_per_gpu": 1, "bits_per_frame": L, "via": "host"},
+            "update_ms": float(np.median(t_upd)) * 1e3, "chainback_ms": float(np.median(t_cb)) * 1e3,
+            "ms_per_step_median": float(np.median(np.asarray(t_upd) + np.asarray(t_cb))) * 1e3,
+            "ns_per_trellis_step_update": float(np.median(t_upd)) / S * 1e9,
+        }
     dt = {"SOFT16": pyoracle.SOFT16, "SOFT8": pyoracle.SOFT8, "HARD8": pyoracle.HARD8}[args.decode_type]
     ocfg = pyoracle.stock_config(dt, code.R)
     pyoracle.ensure_built()
@@ -563,7 +615,6 @@ def host_route_result(args):
     want = ref.run(args.code, ocfg, sym[0], L, simd=pyoracle.SCALAR) if ref else pyoracle.Oracle().decode(code.K, code.R, code.G, ocfg, sym[0], L)
     ok_b = bool(np.array_equal(out, want["bytes"]))
     ok_d = bool(np.array_equal(np.asarray(vitdec.m_decisions).reshape(S, -1), np.asarray(want["decisions"])[:S].reshape(S, -1)))
-    step_ms = elapsed / args.steps * 1e3
     sb = pc.soft_bytes
     frame_bytes = S * code.R * sb + S * 8 + L * 8 + L // 8          # symbols in, decision rows out, one word per step back, bytes out
     result = {
@@ -592,7 +643,7 @@ def host_route_result(args):
                    "chainback_bytes_bit_exact": ok_b, "decision_words_bit_exact": ok_d, "bit_exact": ok_b and ok_d},
         "ber": float(np.unpackbits(out ^ tx[0]).mean()),
     }
-    if ref and not args.no_cpu_baseline:
+    if ref and full and not args.no_cpu_baseline:
         topo = host_cpu_topology()
         res = {}
         for name, simd in (("scalar", pyoracle.SCALAR), ("avx", pyoracle.SIMD_AVX)):
@@ -745,7 +796,7 @@ def main():
         # region: nothing but the synchronisation the contract asks for separates the W warm-up steps from the K timed ones, so the
         # card enters the timed region in the power state the decode itself put it in (with the probe in between, the first eight
         # timed steps ramped from 3.64 to 3.35 ms).  Timing records run through both; the timed region's are the last K.
-        clock_cold = shader_clock()
+        clock_cold = shader_clock() if args.full else (None, None)
         pipe.set_timing(True)
         for _ in range(args.warmup):
             pipe.submit(sym, out)
@@ -761,7 +812,7 @@ def main():
         if world > 1:
             dist.barrier()
         elapsed_local = time.perf_counter() - t0
-        clock_after = shader_clock()
+        clock_after = shader_clock() if args.full else (None, None)
         t_upd, t_cb, t_done = pipe.timing()
         # one record per SUB-batch (the library may feed a batch to the kernels in several launches: sch.sub_batch_frames)
         F_launch = min(F, int(sch.sub_batch_frames))
@@ -906,7 +957,7 @@ def main():
                 done.record(s_cb)
             cb_done[k % NWS] = done
 
-        clock_cold = shader_clock()             # no probe between warm-up and timed region (see the pipeline route above)
+        clock_cold = shader_clock() if args.full else (None, None)   # no probe between warm-up and timed region (see the pipeline route above)
         evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(args.steps)]
         for k in range(args.warmup):
             one_step(k)
@@ -920,7 +971,7 @@ def main():
         if world > 1:
             dist.barrier()
         elapsed_local = time.perf_counter() - t0
-        clock_after = shader_clock()
+        clock_after = shader_clock() if args.full else (None, None)
         upd_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
         cb_ms = float(np.mean([(e[3] if NWS >= 2 else e[1]).elapsed_time(e[2]) for e in evs]))
         t_done = np.asarray([evs[0][0].elapsed_time(e[2]) for e in evs], dtype=np.float64)
@@ -934,6 +985,8 @@ def main():
         def last_decisions(n):
             return 0, dec.export_decisions(n, L, workspace=wss[(args.warmup + args.steps - 1) % NWS])
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, prefix=f"rank{rank}_" if world > 1 else "")
     elapsed = elapsed_local
     step_median_ms = float(np.median(step_times))             # steady state: completion to completion, fill and drain excluded
     per_rank = [float(F) * L * args.steps / elapsed_local / 1e6]
@@ -946,25 +999,27 @@ def main():
         per_rank = [float(r.item()) for r in rates]
 
     # ---- size-independent parity property at full size: decoded bits vs transmitted bits ----
-    lut = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device=dev)
-    bit_errors = int(lut[torch.bitwise_xor(out, tx).long()].sum().item())
-    ber = bit_errors / float(F * L)
+    ber = None
+    if args.full:
+        lut = torch.tensor([bin(i).count("1") for i in range(256)], dtype=torch.int64, device=dev)
+        bit_errors = int(lut[torch.bitwise_xor(out, tx).long()].sum().item())
+        ber = bit_errors / float(F * L)
 
     # every rank reads its own shader clock under load (untimed extra batches) and says where it was pinned
     clock_load = (None, None)
-    if clock_under_load is not None:
+    if clock_under_load is not None and args.full:
         try:
             clock_load = clock_under_load()
         except Exception as e:              # a rank whose probe fails still takes part in the all_gather below
             clock_load = (None, {"error": f"{type(e).__name__}: {e}"})
     sustained = None
-    if sustained_leg is not None and args.sustain_seconds > 0:
+    if sustained_leg is not None and args.full and args.sustain_seconds > 0:
         try:
             sustained = sustained_leg(args.sustain_seconds)
         except Exception as e:
             sustained = {"error": f"{type(e).__name__}: {e}"}
     kernel_clock = None
-    if update_kernel_clock is not None and dec.plan == _lib.PLAN_REG:
+    if update_kernel_clock is not None and args.full and dec.plan == _lib.PLAN_REG:
         try:
             kernel_clock = update_kernel_clock()
         except Exception as e:
@@ -988,7 +1043,7 @@ def main():
     # ---- parity of the last timed launch, on EVERY rank: each one checks frames of ITS OWN shard against the scalar reference
     # (bytes and every decision word); the pass flags and counts are summed over the ranks.  N = 1: 512 frames; N > 1: 64 per rank
     parity = None
-    if args.parity or not args.no_cpu_baseline or world > 1:
+    if args.parity or (args.full and (not args.no_cpu_baseline or world > 1)):
         from oracle import pyoracle
         if world > 1:
             if int(os.environ.get("LOCAL_RANK", "0")) == 0:
@@ -1120,7 +1175,7 @@ def main():
         result["parity"] = parity
     def headline_cpu_baseline():
         # (the CPU leg: 10 - 20 s in which the card idles and drops its clocks -- it runs LAST, behind the other configs' GPU legs)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.code, code, pc, args.decode_type, sym, L, args.cpu_seconds)
             result["speedup_vs_cpu_baseline"] = value / result["cpu_baseline"]["value"]
             if "single_socket_extrapolated_Mbit_s" in result["cpu_baseline"]:
@@ -1129,7 +1184,7 @@ def main():
     # examples/run_benchmark.cpp:168-179).  Only behind the DEFAULT workload at N = 1; the headline's numbers above are complete
     # before any of this runs, and its buffers are freed first.
     default_workload = (args.code, args.decode_type, args.frames, args.bits) == BASELINE_CONFIGS[1][:4] and args.plan == "auto"
-    if world == 1 and args.via == "pipeline" and default_workload and not args.no_extra_configs:
+    if world == 1 and args.via == "pipeline" and default_workload and args.full and not args.no_extra_configs:
         import gc
         pipe.close()
         del pipe, tx, out                   # (the symbols stay for the CPU leg: 2 GB of 288)
@@ -1148,7 +1203,7 @@ def main():
             t0c = time.perf_counter()
             c0 = BASELINE_CONFIGS[0]
             r0 = host_route_result(argparse.Namespace(code=c0[0], decode_type=c0[1], bits=c0[3], ebn0=c0[4], steps=max(args.steps, 200), warmup=max(args.warmup, 20),
-                                                      no_cpu_baseline=args.no_cpu_baseline))
+                                                      no_cpu_baseline=args.no_cpu_baseline, full=True))
             r0["baseline_config"] = 0
             r0["seconds_spent"] = time.perf_counter() - t0c
             extra.insert(0, r0)

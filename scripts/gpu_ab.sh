@@ -5,7 +5,7 @@ A=$1; B=$2; REPS=${3:-2}
 line() { python -c "
 import json,sys
 r=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('$1', round(r['value']), 'Mbit/s step', round(r['ms_per_step'],3), 'median', round(r['ms_per_step_median'],3), 'upd', round(r['update_ms'],3), 'cb', round(r['chainback_ms'],3), 'clk', round(r['clock_mhz']['under_load']))"; }
-BENCH="timeout -k 10 300 python bench.py --no-cpu-baseline --steps 24 --warmup 6"
+BENCH="timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 24 --warmup 6"
 for rep in $(seq $REPS); do
 for lib in $A $B; do
 export VIT_HIP_LIB_PATH=$PWD/$lib

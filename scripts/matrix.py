@@ -21,7 +21,7 @@ for ci, code in enumerate(COMMON_CODES):
         F = int(opt.get("--frames", 65536)) if code.K < 11 else 4096
         steps = int(opt.get("--steps", 12)) if code.K < 9 else 8 if code.K < 11 else 4
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--code", str(ci), "--decode-type", dt, "--frames", str(F), "--bits", "8192",
-               "--steps", str(steps), "--warmup", str(max(2, steps // 3)), "--no-cpu-baseline", "--parity", "--sustain-seconds", "0",
+               "--steps", str(steps), "--warmup", str(max(2, steps // 3)), "--full", "--no-cpu-baseline", "--parity", "--sustain-seconds", "0",
                "--ebn0", "5.0" if dt == "HARD8" else "3.0"]
         t0 = time.time()
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

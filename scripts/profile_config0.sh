@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/prof_config0
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--config 0 --steps 200 --warmup 20 --no-cpu-baseline"
+ARGS="--config 0 --steps 200 --warmup 20 --full --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" --output-format csv -- python3 "$REPO/bench.py" $ARGS > "$OUT/trace.log" 2>&1; echo "trace rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY -d "$OUT/pmc_sq" --output-format csv -- python3 "$REPO/bench.py" $ARGS > "$OUT/pmc_sq.log" 2>&1; echo "pmc rc=$?"
 find "$OUT" -name "*kernel_stats.csv" | head -2

@@ -33,7 +33,7 @@ def short(name):
 
 
 lines = [f"# rocprofv3 summary `{tag}`", "",
-         "Command per pass: `rocprofv3 <pass flags> --output-format csv -- python3 bench.py --steps " + os.environ.get("PROFILE_STEPS", "20") + " --warmup " + os.environ.get("PROFILE_WARMUP", "10") + " --no-cpu-baseline " + " ".join(sys.argv[3:]) + "`",
+         "Command per pass: `rocprofv3 <pass flags> --output-format csv -- python3 bench.py --steps " + os.environ.get("PROFILE_STEPS", "20") + " --warmup " + os.environ.get("PROFILE_WARMUP", "10") + " --full --no-cpu-baseline " + " ".join(sys.argv[3:]) + "`",
          "(scripts/profile.sh; rocprofv3's own averages include the warm-up launches).", ""]
 
 # ---- pass 1: kernel stats ----

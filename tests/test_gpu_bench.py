@@ -58,7 +58,7 @@ def test_gpus_2_spawns_two_ranks_on_one_card():
     """`python bench.py --gpus 2` with no launcher: the parent spawns two fresh rank processes (here both on cuda:0, gloo for
     the collectives -- the RCCL/xGMI form needs two cards) and rank 0 reports the aggregate."""
     r = _json_line(_run("--gpus", "2", "--share-gpu", "--backend", "gloo", "--frames", "4096", "--bits", "1024",
-                        "--steps", "3", "--warmup", "1"))
+                        "--steps", "3", "--warmup", "1", "--full"))
     assert r["n_gpus"] == 2 and r["scaling"] == "weak"
     assert r["ranks"]["world_size"] == 2 and r["ranks"]["ranks_in_blob_allreduce"] == 2
     assert r["ranks"]["blob_checksum_identical_on_all_ranks"] is True
@@ -80,7 +80,7 @@ def test_gpus_2_spawns_two_ranks_on_one_card():
 
 @pytest.mark.gpu
 def test_single_rank_line_is_self_consistent():
-    r = _json_line(_run("--frames", "8192", "--bits", "2048", "--steps", "4", "--warmup", "1", "--cpu-seconds", "2"))
+    r = _json_line(_run("--frames", "8192", "--bits", "2048", "--steps", "4", "--warmup", "1", "--cpu-seconds", "2", "--full"))
     assert r["n_gpus"] == 1 and r["unit"] == "Mbit/s" and r["dtype"] == "u16" and r["vs_baseline"] is None
     bits = 8192 * 2048 * 4
     assert abs(r["value"] - bits / (r["ms_per_step"] * 4e-3) / 1e6) / r["value"] < 1e-6
@@ -109,7 +109,7 @@ def test_headline_line_carries_its_spread_and_both_routes_agree():
     """the default workload (BASELINE configs[1]) through the shipped pipeline API: the per-step times recorded on the device
     bracket their median, the median agrees with the wall-clock figure, and the Python re-implementation of the schedule
     (--via python) lands on the same rate."""
-    a = _json_line(_run("--config", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--parity"))
+    a = _json_line(_run("--config", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--parity", "--full"))
     assert a["parity"]["bit_exact"] and a["parity"]["frames_checked_vs_scalar_reference"] == 512
     # the default workload's line also carries BASELINE configs[2], [3] (one GPU's share) and [4], each timed through the same pipeline
     # API with its own roofline and parity block (the reference runs its whole matrix in one invocation: run_benchmark.cpp:168-179)
@@ -143,7 +143,7 @@ def test_headline_line_carries_its_spread_and_both_routes_agree():
     rv = a["roofline_valu"]
     assert rv["peak_spec"] > rv["peak"] and 0 < rv["frac_of_spec"] < rv["frac"] < 1.0, rv
     assert len(a["ms_per_step_series"]) == 20 and abs(sum(a["ms_per_step_series"]) / 20 - a["ms_per_step"]) < 0.05 * a["ms_per_step"]
-    b = _json_line(_run("--config", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--via", "python"))
+    b = _json_line(_run("--config", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--via", "python", "--full"))
     assert "configs" not in b
     assert b["config"]["via"] == "python"
     # the Python re-implementation queues the same kernels from the interpreter (a few microseconds later per launch): it may
@@ -154,8 +154,31 @@ def test_headline_line_carries_its_spread_and_both_routes_agree():
 @pytest.mark.gpu
 def test_config_presets_name_the_baseline_configs():
     """--config 3 is one GPU's share of the 8-GPU hard-decision run; the small-batch schedule (two updates in flight) serves it"""
-    r = _json_line(_run("--config", "3", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"))
+    r = _json_line(_run("--config", "3", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--full"))
     assert r["dtype"] == "u8" and r["config"]["frames_per_gpu"] == 32768 and r["config"]["bits_per_frame"] == 8192
     assert "HARD8" in r["config"]["workload"]
     assert r["update_launches_in_flight"] == 2 and r["roofline"]["launches_in_flight"] == 2
     assert 0 < r["ber"] < 1e-2
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_only_and_dumps_repeatable_outputs(tmp_path):
+    """without --full the line carries the headline and nothing that needs runs of its own; --dump-outputs writes the decoded
+    bytes of the last timed step, the same on every run with the same arguments"""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _json_line(_run("--frames", "4096", "--bits", "2048", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in r, key
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "Mbit/s" and r["higher_is_better"] is True and r["dtype"] == "u16"
+        assert abs(r["value"] - 4096 * 2048 * 3 / (r["ms_per_step"] * 3e-3) / 1e6) / r["value"] < 1e-6
+        assert len(r["ms_per_step_series"]) == 3
+        assert not {"configs", "cpu_baseline", "parity"} & set(r) and r["sustained"] is None and r["ber"] is None
+        got = np.load(d / "decoded_bytes.npy")
+        assert got.dtype == np.float32 and got.shape == (4096, 2048 // 8)
+        assert np.array_equal(np.load(d / "decoded_frame_index.npy"), np.arange(4096))
+        dumps.append(got)
+    assert np.array_equal(dumps[0], dumps[1])
