@@ -28,6 +28,9 @@
  *   vit_hip_update_batch_resume  update() called again on a decoder that already holds state: the cursor
  *                             m_current_decoded_bit and the metrics carry over
  *                                                                 viterbi_decoder_scalar.h:29-55 (:37-54 the cursor)
+ *   vit_hip_decode_tail_biting_batch  tail-biting frames (no tail, the encoder starts in the state its last K-1 bits leave):
+ *                             no reference counterpart -- the reference decodes terminated frames only; this call is written
+ *                             in terms of its reset / update / chainback (rule below), with _tail_biting_workspace_bytes
  *   vit_hip_broadcast_table   "Branch table can be shared between multiple decoders"   README.md:14,
  *                             viterbi_branch_table.h:17-18, one decoder per worker examples/run_benchmark.cpp:193-197:
  *                             here the workers are GPUs and the table travels once over RCCL/xGMI
@@ -329,6 +332,34 @@ int vit_hip_reset_batch(vit_hip_handle h, size_t frames, const uint32_t* d_start
 int vit_hip_update_batch_resume(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_stride, size_t frames,
                                 size_t first_step, size_t n_steps, size_t L, void* d_workspace, size_t workspace_bytes,
                                 void* d_metrics_inout, uint64_t* d_renorm_sum, vit_hip_stream_t stream);
+
+/* ---- batched tail-biting frames ("wrap-around Viterbi with fixed extension", one pass) ------------------------------------
+ * A tail-biting codeword of L info bits x[0..L) is L*R symbols with no tail: the encoder starts in the state x[L-K+1..L) leaves,
+ * so the path starts and ends in the same, unknown state (LTE PBCH / PDCCH use the K = 7, R = 1/3 stock code this way).  Rule,
+ * bit-exact, in terms of the reference's reset / update / chainback:
+ *   - extension: S_ext = head + L + tail steps, ext[e] = symbols[(e - head) mod L] (wraps more than once when L < head);
+ *   - metrics: every state starts at initial_start_error (reset() with every state a start state);
+ *   - update() over all S_ext steps (the plan's own kernels, resumed from those metrics);
+ *   - end state: the smallest final metric, compared as unsigned error_t, the lowest state on a tie;
+ *   - chainback(ext_bytes, L_ext = S_ext - (K-1), end_state); the output is bits [head, head + L) of ext_bytes, MSB-first,
+ *     ceil(L/8) bytes per frame, pad bits 0;
+ *   - d_tail_biting_ok[f] = 1 when ext bits [head-K+1, head) equal ext bits [head+L-K+1, head+L): the decoded path enters and
+ *     leaves the window in the same state (a valid tail-biting codeword).
+ * L >= K, head >= K-1 and tail >= K-1, else VIT_HIP_ERR_INVALID_ARG and nothing is launched.  8*(K-1) for both (48 at K = 7) is
+ * the default of the C++ and Python layers.
+ *   d_symbols        [frames][L][R] soft_t
+ *   d_workspace      >= vit_hip_tail_biting_workspace_bytes(h, frames, L, head, tail) bytes, 256-byte aligned
+ *                    (VIT_HIP_ERR_WORKSPACE otherwise); it holds, each part 256-byte aligned: the plan's decision workspace for
+ *                    L_ext at offset 0, the extended symbols, the [frames][N] metrics, the end states, the extended chainback bytes
+ *   d_bytes_out      [frames][ceil(L/8)]
+ *   d_end_state_out  [frames] uint32 or NULL: the selected end states
+ *   d_tail_biting_ok [frames] uint8 or NULL
+ * A batch call like the others: it only enqueues (five launches on `stream`), several may be in flight on one handle, each with
+ * its own workspace.  vit_hip_tail_biting_workspace_bytes returns 0 for arguments the decode call rejects. */
+size_t vit_hip_tail_biting_workspace_bytes(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail);
+int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, size_t frames, size_t L, size_t head,
+                                     size_t tail, void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out,
+                                     uint32_t* d_end_state_out, uint8_t* d_tail_biting_ok, vit_hip_stream_t stream);
 
 /* ---- multi-GPU set-up for C/C++ hosts ----------------------------------------------------------------------------------- */
 

@@ -72,6 +72,18 @@ public:
                                           d_workspace, workspace_size, d_metrics_inout, d_renorm_sum, stream),
               "vit_hip_update_batch_resume");
     }
+    // tail-biting frames (vit_hip_decode_tail_biting_batch): d_symbols [frames][total_bits][R], no tail; wrap-around Viterbi with
+    // `head` steps of extension before the frame and `tail` after it (0: the default 8*(K-1)).  The workspace is caller-owned.
+    size_t tail_biting_workspace_bytes(size_t frames, size_t total_bits, size_t head = 0, size_t tail = 0) const {
+        return vit_hip_tail_biting_workspace_bytes(m_hip, frames, total_bits, extension(head), extension(tail));
+    }
+    void decode_tail_biting(const soft_t* d_symbols, size_t frames, size_t total_bits, void* d_workspace, size_t workspace_size,
+                            uint8_t* d_bytes_out, uint32_t* d_end_state_out = nullptr, uint8_t* d_tail_biting_ok = nullptr,
+                            size_t head = 0, size_t tail = 0, void* stream = nullptr) {
+        check(vit_hip_decode_tail_biting_batch(m_hip, d_symbols, frames, total_bits, extension(head), extension(tail), d_workspace,
+                                               workspace_size, d_bytes_out, d_end_state_out, d_tail_biting_ok, stream),
+              "vit_hip_decode_tail_biting_batch");
+    }
     // test / measurement harness on the device: the BER harness's frame generator (examples/run_snr_ber.cpp:311-359) and
     // get_total_bit_errors (examples/helpers/test_helpers.h:95-104)
     void synth(size_t frames, size_t total_bits, uint64_t seed, uint64_t first_frame, float ebn0_db, bool noise_free,
@@ -96,6 +108,7 @@ public:
     const char* plan_note() const { return vit_hip_plan_note(m_hip); }
 
 private:
+    static size_t extension(size_t steps) { return steps ? steps : 8 * (K - 1); }
     static void check(int rc, const char* what) {
         if (rc != VIT_HIP_OK) {
             fprintf(stderr, "viterbi_hip: %s failed (%d): %s\n", what, rc, vit_hip_last_error());

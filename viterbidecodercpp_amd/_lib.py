@@ -29,6 +29,7 @@ EXPORTS = [
     "vit_hip_pipeline_wait_event", "vit_hip_get_kernel_resources", "vit_hip_list_kernels",
     "vit_hip_chainback_batch_ex", "vit_hip_pipeline_create_ex", "vit_hip_pipeline_get_schedule_v2", "vit_hip_plan_note",
     "vit_hip_precompile", "vit_hip_update_host_lazy", "vit_hip_chainback_host_lazy", "vit_hip_fetch_decisions_host",
+    "vit_hip_tail_biting_workspace_bytes", "vit_hip_decode_tail_biting_batch",
 ]
 
 
@@ -116,6 +117,9 @@ def load():
     L.vit_hip_depuncture_batch.argtypes = [vp, vp, sz, vp, sz, sz, vp, vp]
     L.vit_hip_reset_batch.argtypes = [vp, sz, vp, vp, vp]
     L.vit_hip_update_batch_resume.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, sz, vp, vp, vp]
+    L.vit_hip_tail_biting_workspace_bytes.restype = sz
+    L.vit_hip_tail_biting_workspace_bytes.argtypes = [vp, sz, sz, sz, sz]
+    L.vit_hip_decode_tail_biting_batch.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, vp, vp, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

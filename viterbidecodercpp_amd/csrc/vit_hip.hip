@@ -23,6 +23,7 @@
 #include "kernels_one.hpp"
 #include "kernels_reg.hpp"
 #include "kernels_synth.hpp"
+#include "kernels_tb.hpp"
 #include "reg_jit.hpp"
 
 namespace {
@@ -709,6 +710,108 @@ int vit_hip_depuncture_batch(vit_hip_handle h, const void* d_punctured, size_t p
         hipLaunchKernelGGL(vit::depuncture_kernel<int8_t>, dim3(blocks), dim3(256), 0, st, (const int8_t*)d_punctured,
                            punctured_per_frame, d_source_index, symbols_per_frame, frames, (int8_t*)d_symbols_out);
     VIT_HIP_CHECK(hipGetLastError());
+    return VIT_HIP_OK;
+}
+
+namespace {
+// the caller-owned workspace of one tail-biting call, every sub-buffer 256-byte aligned (include/vit_hip.h)
+struct TbLayout {
+    size_t S_ext = 0, L_ext = 0, nbe = 0;          // extended steps, extended chainback bits, its bytes per frame
+    size_t dec = 0, ext = 0, met = 0, end = 0, bytes = 0, total = 0;   // offsets, and the whole size
+};
+
+// argument rule of the tail-biting entry points: L >= K, head and tail >= K-1, and sizes the launchers' 32-bit counters hold
+const char* tb_invalid(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail) {
+    const size_t K = (size_t)h->K;
+    if (L < K) return "tail-biting frames need L >= K";
+    if (head < K - 1 || tail < K - 1) return "head and tail must be >= K-1";
+    if (frames > 0x7FFFFFF0u || L > 0x10000000u || head > 0x10000000u || tail > 0x10000000u) return "batch too large";
+    return nullptr;
+}
+
+void tb_layout(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail, TbLayout& o) {
+    o.S_ext = head + L + tail;
+    o.L_ext = o.S_ext - ((size_t)h->K - 1);
+    o.nbe = (o.L_ext + 7) / 8;
+    o.dec = 0;
+    o.ext = align_up(vit_hip_workspace_bytes(h, frames, o.L_ext), 256);
+    o.met = o.ext + align_up(frames * o.S_ext * (size_t)h->R * (size_t)h->soft_bytes, 256);
+    o.end = o.met + align_up(frames * (size_t)h->N * (size_t)h->error_bytes, 256);
+    o.bytes = o.end + align_up(frames * sizeof(uint32_t), 256);
+    o.total = o.bytes + align_up(frames * o.nbe, 256);
+}
+}  // namespace
+
+size_t vit_hip_tail_biting_workspace_bytes(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail) {
+    if (!h || tb_invalid(h, frames, L, head, tail)) return 0;
+    TbLayout lay;
+    tb_layout(h, frames, L, head, tail, lay);
+    return lay.total;
+}
+
+int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, size_t frames, size_t L, size_t head, size_t tail,
+                                     void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, uint32_t* d_end_state_out,
+                                     uint8_t* d_tail_biting_ok, vit_hip_stream_t stream) {
+    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
+    if (const char* why = tb_invalid(h, frames, L, head, tail)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
+    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
+    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    TbLayout lay;
+    tb_layout(h, frames, L, head, tail, lay);
+    if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
+    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (frames == 0) return VIT_HIP_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(VIT_HIP_ERR_RUNTIME, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)d_workspace;
+    void* ext = ws + lay.ext;
+    void* met = ws + lay.met;
+    uint32_t* end = (uint32_t*)(ws + lay.end);
+    uint8_t* ext_bytes = ws + lay.bytes;
+
+    // 1. the extended symbols and every state a start state
+    vit::TbGatherArgs g{};
+    g.symbols = d_symbols;
+    g.ext = ext;
+    g.metrics = met;
+    g.ext_elems = (uint64_t)frames * lay.S_ext * (uint64_t)h->R;
+    g.gather_chunks = (g.ext_elems * (uint64_t)h->soft_bytes + 15) / 16;
+    g.metric_bytes = (uint64_t)frames * (uint64_t)h->N * (uint64_t)h->error_bytes;
+    g.total_chunks = g.gather_chunks + (g.metric_bytes + 15) / 16;
+    g.L = (uint32_t)L; g.R = (uint32_t)h->R; g.S_ext = (uint32_t)lay.S_ext;
+    g.shift = (uint32_t)((L - head % L) % L);
+    const uint32_t start = h->cfg_raw[1];
+    g.fill = h->error_bytes == 2 ? (start & 0xFFFFu) * 0x00010001u : (start & 0xFFu) * 0x01010101u;
+    if (vit::tb_launch_gather(h->soft_bytes, g, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting gather launch failed");
+
+    // 2. the plan's own update over the whole extension, resumed in place from those metrics (every plan resumes: PLAN_LDS in place)
+    int rc = update_batch_impl(h, ext, 0, frames, 0, lay.S_ext, lay.L_ext, ws, lay.ext, met, met, nullptr, nullptr, stream);
+    if (rc != VIT_HIP_OK) return rc;
+
+    // 3. end state = smallest final metric
+    vit::TbSelectArgs s{};
+    s.metrics = met;
+    s.end_ws = end;
+    s.end_out = d_end_state_out;
+    s.frames = (uint32_t)frames;
+    s.log2N = (uint32_t)(h->K - 1);
+    if (vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting end-state launch failed");
+
+    // 4. the plan's own chainback over the extension from those states
+    rc = chainback_batch_impl(h, ws, frames, lay.L_ext, ext_bytes, end, stream, 0);
+    if (rc != VIT_HIP_OK) return rc;
+
+    // 5. the window [head, head + L) and the tail-biting flag
+    vit::TbWindowArgs w{};
+    w.ext_bytes = ext_bytes;
+    w.out = d_bytes_out;
+    w.ok = d_tail_biting_ok;
+    w.nbe = (uint32_t)lay.nbe;
+    w.nb = (uint32_t)((L + 7) / 8);
+    w.total = (uint64_t)frames * w.nb;
+    w.L = (uint32_t)L; w.head = (uint32_t)head; w.K = (uint32_t)h->K;
+    if (vit::tb_launch_window(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting window launch failed");
     return VIT_HIP_OK;
 }
 

@@ -468,6 +468,55 @@ class BatchDecoder:
             C.c_void_p(rs.data_ptr()) if rs is not None else None, None, self._stream()))
         return (out, met, rs) if want_metrics else out
 
+    def tail_biting_workspace_bytes(self, frames: int, L: int, head: int = None, tail: int = None) -> int:
+        head, tail = self._tb_extension(head, tail)
+        return _lib.load().vit_hip_tail_biting_workspace_bytes(self._handle._h, frames, L, head, tail)
+
+    def _tb_extension(self, head, tail):
+        d = 8 * (self.K - 1)                      # the default extension: byte-aligned, 48 steps at K = 7
+        return (d if head is None else int(head)), (d if tail is None else int(tail))
+
+    def decode_tail_biting(self, symbols, L: int, head: int = None, tail: int = None, out=None, end_state_out=None, ok_out=None,
+                           workspace=None):
+        """tail-biting frames (no tail; the encoder starts in the state the frame's last K-1 bits leave): symbols [F][L][R] ->
+        bytes [F][ceil(L/8)] (vit_hip_decode_tail_biting_batch: wrap-around Viterbi with a fixed extension of `head` steps before
+        and `tail` after the frame, default 8*(K-1) each).  end_state_out / ok_out: [F] int32 / uint8 device tensors, or True
+        to have them allocated; either one asked for returns (bytes, end_state, ok), where ok[f] = 1 when the decoded path is a
+        valid tail-biting codeword."""
+        t = self.torch
+        head, tail = self._tb_extension(head, tail)
+        frames = self._check_symbols(symbols, L)
+        need = self.tail_biting_workspace_bytes(frames, L, head, tail)
+        if need == 0:
+            raise ValueError(f"tail-biting decoding needs L >= K and head, tail >= K-1 (K = {self.K})")
+        if workspace is not None:
+            if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
+                raise ValueError("workspace too small or not 256-byte aligned")
+            ws = workspace
+        else:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
+            ws = self._ws
+        if out is None:
+            out = t.empty((frames, (L + 7) // 8), dtype=t.uint8, device=self.device)
+        want_extra = end_state_out is not None or ok_out is not None
+        if want_extra:
+            if end_state_out is None or end_state_out is True:
+                end_state_out = t.empty(frames, dtype=t.int32, device=self.device)
+            if ok_out is None or ok_out is True:
+                ok_out = t.empty(frames, dtype=t.uint8, device=self.device)
+        for name, x, dt, n in (("out", out, t.uint8, frames * ((L + 7) // 8)), ("end_state_out", end_state_out, t.int32, frames),
+                               ("ok_out", ok_out, t.uint8, frames)):
+            if x is not None and (x.dtype != dt or not x.is_cuda or not x.is_contiguous() or x.numel() != n):
+                raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor of {n} elements")
+        _lib.check(_lib.load().vit_hip_decode_tail_biting_batch(
+            self._handle._h, C.c_void_p(symbols.data_ptr()), frames, L, head, tail, C.c_void_p(ws.data_ptr()),
+            ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()),
+            C.c_void_p(end_state_out.data_ptr()) if want_extra else None, C.c_void_p(ok_out.data_ptr()) if want_extra else None,
+            self._stream()))
+        return (out, end_state_out, ok_out) if want_extra else out
+
     def depuncture(self, punctured, mask, out=None):
         """Depuncturing front-end (examples/helpers/puncture_code_helpers.h:17-55) for a batch: `punctured` is the device
         tensor [F][P] of transmitted symbols, `mask` the puncturing vector over one whole frame (truthy = transmitted, one

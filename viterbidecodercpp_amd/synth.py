@@ -42,6 +42,27 @@ def encode_bits_numpy(K: int, R: int, G, data: np.ndarray) -> np.ndarray:
     return out
 
 
+def encode_tail_biting_numpy(K: int, R: int, G, bits: np.ndarray) -> np.ndarray:
+    """tail-biting codewords: bits [F][L] (0/1, L >= K) -> coded bits [F][L][R] uint8 (0/1), no tail.  The zero-start encoder of
+    encode_bits_numpy runs over x[L-K+1:] ++ x and the outputs of steps K-1 .. K-2+L are kept: the encoder starts in the state the
+    frame's last K-1 bits leave (vit_hip_decode_tail_biting_batch decodes these)."""
+    x = np.ascontiguousarray(bits, dtype=np.uint8)
+    if x.ndim == 1:
+        x = x[None, :]
+    F, L = x.shape
+    if L < K:
+        raise ValueError("tail-biting frames need L >= K")
+    y = np.concatenate([x[:, L - K + 1:], x], axis=1)          # K-1 bits of history, then the frame
+    out = np.zeros((F, L, R), dtype=np.uint8)
+    for i in range(R):
+        acc = np.zeros((F, L), dtype=np.uint8)
+        for k in range(K):                                     # register bit k holds the input bit from k steps ago
+            if (int(G[i]) >> k) & 1:
+                acc ^= y[:, K - 1 - k:K - 1 - k + L]
+        out[:, :, i] = acc
+    return out
+
+
 def _round_half_away(x):
     return np.sign(x) * np.floor(np.abs(x) + np.float32(0.5))
 
