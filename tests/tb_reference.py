@@ -14,8 +14,9 @@ def default_extension(K):
     return 8 * (K - 1)
 
 
-def tb_reference(oracle, code, ocfg, sym, L, head=None, tail=None):
-    """sym [F][L][R] soft -> (bytes [F][ceil(L/8)] uint8, end_state [F] uint32, ok [F] uint8)"""
+def tb_reference(oracle, code, ocfg, sym, L, head=None, tail=None, want_metrics=False):
+    """sym [F][L][R] soft -> (bytes [F][ceil(L/8)] uint8, end_state [F] uint32, ok [F] uint8), and with want_metrics the final
+    metrics [F][N] uint32 the end state is chosen from"""
     K, R = code.K, code.R
     head = default_extension(K) if head is None else head
     tail = default_extension(K) if tail is None else tail
@@ -30,6 +31,7 @@ def tb_reference(oracle, code, ocfg, sym, L, head=None, tail=None):
     out = np.zeros((F, nb), dtype=np.uint8)
     ends = np.zeros(F, dtype=np.uint32)
     ok = np.zeros(F, dtype=np.uint8)
+    final = np.zeros((F, N), dtype=np.uint32)
     for f in range(F):
         ext = np.ascontiguousarray(sym[f][idx])
         metrics = np.full(N, ocfg.initial_start_error, dtype=np.uint32)
@@ -39,7 +41,8 @@ def tb_reference(oracle, code, ocfg, sym, L, head=None, tail=None):
         out[f] = np.packbits(bits[head:head + L], bitorder="big")[:nb]
         ends[f] = end
         ok[f] = 1 if np.array_equal(bits[head - K + 1:head], bits[head + L - K + 1:head + L]) else 0
-    return out, ends, ok
+        final[f] = metrics
+    return (out, ends, ok, final) if want_metrics else (out, ends, ok)
 
 
 def ml_tail_biting(code, sym, L):

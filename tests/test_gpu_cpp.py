@@ -11,7 +11,8 @@ CPP = os.path.join(ROOT, "tests", "cpp")
 
 
 def _ensure_built():
-    if not all(os.path.exists(os.path.join(CPP, n)) for n in ("run_simple_hip", "run_tests_hip", "run_batch_hip", "run_multi_gpu_hip", "run_stream_hip")):
+    if not all(os.path.exists(os.path.join(CPP, n)) for n in ("run_simple_hip", "run_tests_hip", "run_batch_hip", "run_tail_biting_hip",
+                                                              "run_multi_gpu_hip", "run_stream_hip")):
         subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "liboracle.so"], check=True, capture_output=True)
         subprocess.run(["make", "-C", CPP], check=True, capture_output=True)
 
@@ -22,6 +23,7 @@ def test_cpp_programs_build():
     assert os.access(os.path.join(CPP, "run_simple_hip"), os.X_OK)
     assert os.access(os.path.join(CPP, "run_tests_hip"), os.X_OK)
     assert os.access(os.path.join(CPP, "run_batch_hip"), os.X_OK)
+    assert os.access(os.path.join(CPP, "run_tail_biting_hip"), os.X_OK)
     assert os.access(os.path.join(CPP, "run_multi_gpu_hip"), os.X_OK)
 
 
@@ -62,6 +64,16 @@ def test_run_batch_hip():
     p = subprocess.run([os.path.join(CPP, "run_batch_hip")], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "mismatching frames=0" in p.stdout and p.stdout.strip().endswith("PASS")
+
+
+@pytest.mark.gpu
+def test_run_tail_biting_hip():
+    """ViterbiDecoder_HIP_Batch::decode_tail_biting from C++ (LTE soft16 at the default extension, K = 2 soft8 at an explicit one)
+    vs the tail-biting rule restated on the oracle's update / chainback: bytes, end states and flags of every frame."""
+    _ensure_built()
+    p = subprocess.run([os.path.join(CPP, "run_tail_biting_hip")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.count("mismatching frames=0") == 2 and p.stdout.strip().endswith("PASS"), p.stdout
 
 
 @pytest.mark.gpu

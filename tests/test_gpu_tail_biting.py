@@ -7,7 +7,7 @@ import time
 import numpy as np
 import pytest
 
-from viterbidecodercpp_amd import COMMON_CODES, BatchDecoder, Code, _lib
+from viterbidecodercpp_amd import COMMON_CODES, BatchDecoder, Code, ViterbiBranchTable, ViterbiDecoder_Config, _lib
 from tests.helpers import DECODE_TYPES, default_ebn0, make_table_config, oracle_cfg
 from tests.tb_reference import tb_frames, tb_reference
 
@@ -240,3 +240,252 @@ def test_side_pass_overhead():
     print(f"tail-biting {t_tb * 1e3:.3f} ms, update + chainback of the extended batch {t_plain * 1e3:.3f} ms, "
           f"ratio {t_tb / t_plain:.3f}")
     assert t_tb <= OVERHEAD_BOUND * t_plain, (t_tb, t_plain)
+
+
+# ---- every K = 2 .. 16, R = 1 .. 8, both widths, every plan family -----------------------------------------------------------
+# Polynomial sets from the other suites only, so that nothing is compiled on the GPU host: PLAN_REG at the run-time instantiated sets
+# of tests/jit_codes.txt (at the width listed there), GENERIC at the rate-1 sets of test_gpu_generic.py::SETS, PLAN_LDS2 at the sets
+# of test_gpu_parity.py::test_lds2_plan_large_k and the K = 16 set of test_gpu_fuzz.py, PLAN_LDS at K = 2, K6 R7 (test_gpu_api.py),
+# K7 R8 (test_gpu_latency.py), K15 and K16.
+REG, GENERIC, LDS, LDS2 = "REG", "GENERIC", "LDS", "LDS2"
+K16 = (46749, 58851)
+SWEEP = [
+    (2, 2, (0o3, 0o1), "SOFT16", REG), (2, 3, (0o3, 0o2, 0o3), "HARD8", REG),
+    (2, 2, (0o3, 0o1), "SOFT16", LDS), (2, 2, (0o3, 0o1), "SOFT8", LDS),
+    (3, 4, (0o5, 0o7, 0o7, 0o5), "HARD8", REG), (4, 2, (0o15, 0o17), "SOFT16", REG),
+    (5, 5, (0o27, 0o31, 0o33, 0o37, 0o35), "SOFT16", REG), (5, 1, (0o27,), "HARD8", GENERIC),
+    (6, 6, (0o65, 0o57, 0o75, 0o53, 0o71, 0o47), "HARD8", REG), (6, 7, (0o65, 0o57, 0o75, 0o53, 0o71, 0o47, 0o77), "SOFT16", LDS),
+    (7, 5, (0o171, 0o133, 0o165, 0o117, 0o135), "SOFT8", REG), (7, 6, (0o171, 0o133, 0o165, 0o117, 0o135, 0o157), "SOFT16", REG),
+    (7, 1, (0o165,), "SOFT16", GENERIC),
+    (7, 8, (0o171, 0o133, 0o165, 0o117, 0o135, 0o157, 0o145, 0o173), "SOFT8", LDS),
+    (8, 2, (0o371, 0o247), "SOFT8", REG), (8, 6, (0o371, 0o247, 0o367, 0o331, 0o225, 0o313), "SOFT16", REG),
+    (8, 1, (0o371,), "SOFT8", GENERIC),
+    (9, 5, (0o557, 0o663, 0o711, 0o561, 0o753), "HARD8", REG), (9, 6, (0o557, 0o663, 0o711, 0o561, 0o753, 0o715), "SOFT16", REG),
+    (9, 1, (0o753,), "SOFT16", GENERIC),
+    (10, 5, (0o1167, 0o1545, 0o1117, 0o1365, 0o1633), "SOFT16", LDS2),
+    (11, 5, (0o3345, 0o3613, 0o2671, 0o3175, 0o2353), "SOFT8", LDS2),
+    (11, 6, (0o3345, 0o3613, 0o2671, 0o3175, 0o2353, 0o3661), "HARD8", LDS2),
+    (12, 2, (0o4335, 0o5723), "SOFT8", LDS2), (12, 5, (0o4335, 0o5723, 0o6265, 0o7173, 0o5537), "SOFT16", LDS2),
+    (12, 6, (0o4335, 0o5723, 0o6265, 0o7173, 0o5537, 0o6747), "HARD8", LDS2),
+    (13, 2, (0o10533, 0o17661), "SOFT16", LDS2), (13, 6, (0o10533, 0o10675, 0o17661, 0o13271, 0o15353, 0o16475), "SOFT8", LDS2),
+    (14, 2, (0o21645, 0o35661), "SOFT16", LDS2),
+    (15, 6, COMMON_CODES[7].G, "SOFT16", LDS),
+    (16, 2, K16, "HARD8", LDS2), (16, 2, K16, "SOFT16", LDS),
+]
+PLAN_OF = {REG: _lib.PLAN_REG, GENERIC: _lib.PLAN_REG, LDS: _lib.PLAN_LDS, LDS2: _lib.PLAN_LDS2}
+
+
+def sweep_cases(K):
+    """(F, L, head, tail): F = 1 and 2, frame counts that leave a partial tile or frame pair; L = K, head > L, heads that are no
+    multiple of 8.  K >= 14: a few frames and no L = 1000, as elsewhere in the suite."""
+    if K >= 14:
+        return [(1, K, None, None), (2, 41, K - 1, K - 1), (3, K + 1, 3 * (K + 1) + 5, K - 1), (2, 40, K + 3, K)]
+    Fs = [1, 2, 70, 130, 67, 3, 150] if K <= 9 else [1, 2, 7, 3, 5, 2, 1]
+    return [(F,) + c for F, c in zip(Fs, extension_cases(K))]
+
+
+@pytest.mark.parametrize("K,R,G,decode_type,family", SWEEP, ids=lambda x: x if isinstance(x, (int, str)) else None)
+def test_sweep_k_rate_width_plan(oracle, monkeypatch, tmp_path, K, R, G, decode_type, family):
+    if family == GENERIC:
+        _no_compiler(monkeypatch, tmp_path)
+    code = Code(f"K{K}R{R}", K, R, tuple(G))
+    pc, table, config = make_table_config(code, decode_type)
+    dec = BatchDecoder(table, config) if family == GENERIC else BatchDecoder(table, config, plan=PLAN_OF[family])
+    assert dec.plan == PLAN_OF[family], dec.plan_note
+    assert ("GENERIC" in dec.plan_note) == (family == GENERIC), dec.plan_note
+    for k, (F, L, head, tail) in enumerate(sweep_cases(K)):
+        decode_and_compare(oracle, code, decode_type, F, L, head, tail, seed=100 * K + 10 * R + k, dec=dec)
+    assert dec.plan == PLAN_OF[family]
+
+
+# ---- random decoder configs --------------------------------------------------------------------------------------------------
+RANDOM_CASES = [
+    (COMMON_CODES[1], REG), (COMMON_CODES[2], REG), (COMMON_CODES[5], REG), (Code("custom K7", 7, 2, (0o147, 0o135)), GENERIC),
+    (Code("K2", 2, 2, (0o3, 0o1)), LDS), (Code("K11", 11, 2, (0o3345, 0o3613)), LDS2), (Code("K16", 16, 2, K16), LDS2),
+]
+
+
+@pytest.mark.parametrize("width", [2, 1])
+@pytest.mark.parametrize("case", range(len(RANDOM_CASES)))
+def test_random_configs(oracle, monkeypatch, tmp_path, case, width):
+    """any ViterbiDecoder_Config (tests/test_gpu_fuzz.py::random_config: thresholds 0, type-max and random; wrapping error_t
+    arithmetic), in-range and full-type-range symbols, random head / tail in [K-1, 3L]: every metric starts at
+    initial_start_error and the end state is the unsigned argmin of whatever the arithmetic left"""
+    import torch
+    from tests.test_gpu_fuzz import random_config
+
+    code, family = RANDOM_CASES[case]
+    if family == GENERIC:
+        _no_compiler(monkeypatch, tmp_path)
+    K, R = code.K, code.R
+    rng = np.random.default_rng(7000 + 10 * case + width)
+    sdt = np.int16 if width == 2 else np.int8
+    lim = 1 << (8 * width - 1)
+    for trial in range(4):
+        cfg = random_config(rng, width, trial)
+        table = ViterbiBranchTable(K, R, code.G, cfg.high, cfg.low, sdt)
+        config = ViterbiDecoder_Config(cfg.max_error, cfg.initial_start_error, cfg.initial_non_start_error,
+                                       cfg.renormalisation_threshold, np.uint16 if width == 2 else np.uint8)
+        dec = BatchDecoder(table, config) if family == GENERIC else BatchDecoder(table, config, plan=PLAN_OF[family])
+        assert dec.plan == PLAN_OF[family] and ("GENERIC" in dec.plan_note) == (family == GENERIC), dec.plan_note
+        F = int(rng.integers(1, 40)) if K < 11 else int(rng.integers(1, 4))
+        L = int(rng.integers(K, 60)) if K < 14 else int(rng.integers(K, 24))
+        head, tail = (int(x) for x in rng.integers(K - 1, 3 * L + 1, size=2))
+        if trial % 2 == 0:
+            sym = rng.integers(cfg.low, cfg.high + 1, size=(F, L, R)).astype(sdt)
+        else:
+            sym = rng.integers(-lim, lim, size=(F, L, R)).astype(sdt)
+        out, ends, ok = dec.decode_tail_biting(torch.from_numpy(sym).cuda(), L, head, tail, end_state_out=True, ok_out=True)
+        torch.cuda.synchronize()
+        want_out, want_ends, want_ok = tb_reference(oracle, code, cfg, sym, L, head, tail)
+        tag = (code.name, family, trial, F, L, head, tail, cfg)
+        assert np.array_equal(out.cpu().numpy(), want_out), tag
+        assert np.array_equal(ends.cpu().numpy().view(np.uint32), want_ends), tag
+        assert np.array_equal(ok.cpu().numpy(), want_ok), tag
+
+
+# ---- ties in the argmin across lanes and wavefronts ---------------------------------------------------------------------------
+def select_groups(K, error_bytes, states):
+    """(lanes, wavefronts) of the end-state pass (csrc/kernels_tb.hpp) that hold these states: K <= 9 one lane per VB bytes of a
+    frame's metrics, VB = min(16, N * sizeof(error_t)); K >= 10 16-byte chunk c goes to thread c mod 256, wavefront (c mod 256) / 64"""
+    N = 1 << (K - 1)
+    if K <= 9:
+        V = min(16, N * error_bytes) // error_bytes
+        return {s // V for s in states}, {0}
+    c = [s // (16 // error_bytes) for s in states]
+    return set(c), {(x % 256) // 64 for x in c}
+
+
+@pytest.mark.parametrize("decode_type", ["SOFT16", "SOFT8"])
+@pytest.mark.parametrize("code,j", [(COMMON_CODES[3], 5), (COMMON_CODES[5], 6), (Code("K11", 11, 2, (0o2565, 0o3043)), 10),
+                                    (Code("K16", 16, 2, K16), 13)], ids=["K7", "K9", "K11", "K16"])
+def test_argmin_ties_across_lanes_and_wavefronts(oracle, code, j, decode_type):
+    """the last j steps of the extension are erasures (symbol 0: every branch costs the same), so the 2^j states the best state
+    reaches over them end on the same minimum -- an aligned block of states (next = (state << 1 | bit) mod N) that spans several
+    lanes of the end-state pass, and several wavefronts where the frame's metrics have them.  The lowest state of the block wins."""
+    import torch
+
+    K = code.K
+    pc, table, config = make_table_config(code, decode_type)
+    dec = BatchDecoder(table, config)
+    F = 40 if K <= 9 else 3
+    for L, head, tail in ((40, None, None), (K + 1, 2 * K + 3, K + j)):
+        hd = 8 * (K - 1) if head is None else head
+        tl = 8 * (K - 1) if tail is None else tail
+        S_ext = hd + L + tl
+        _, sym = tb_frames(code, pc, F, L, default_ebn0(code, decode_type), seed=K + L)
+        for i in range(j):
+            sym[:, (S_ext - 1 - i - hd) % L] = 0
+        out, ends, ok = dec.decode_tail_biting(torch.from_numpy(sym).cuda(), L, head, tail, end_state_out=True, ok_out=True)
+        torch.cuda.synchronize()
+        want_out, want_ends, want_ok, final = tb_reference(oracle, code, oracle_cfg(decode_type, code.R), sym, L, head, tail,
+                                                           want_metrics=True)
+        for f in range(F):                                  # the ties are real, and cross the boundaries they are meant to
+            tied = np.flatnonzero(final[f] == final[f].min())
+            lanes, waves = select_groups(K, pc.error_bytes, tied)
+            _, all_waves = select_groups(K, pc.error_bytes, range(1 << (K - 1)))
+            assert len(tied) >= 2 and len(lanes) >= 2, (f, tied)
+            assert len(waves) >= min(2, len(all_waves)), (f, tied, waves)
+        tag = (code.name, decode_type, L, head, tail, _lib.PLAN_NAMES[dec.plan])
+        assert np.array_equal(ends.cpu().numpy().view(np.uint32), want_ends), tag
+        assert np.array_equal(out.cpu().numpy(), want_out), tag
+        assert np.array_equal(ok.cpu().numpy(), want_ok), tag
+
+
+# ---- outputs and workspace that hold stale bytes ------------------------------------------------------------------------------
+POISON_CASES = [(COMMON_CODES[3], "SOFT16", REG), (Code("custom K7", 7, 2, (0o147, 0o135)), "SOFT8", GENERIC),
+                (Code("K2", 2, 2, (0o3, 0o1)), "SOFT8", LDS), (Code("K2", 2, 2, (0o3, 0o1)), "SOFT16", LDS),
+                (Code("K11", 11, 2, (0o2565, 0o3043)), "HARD8", LDS2)]
+
+
+@pytest.mark.parametrize("case", range(len(POISON_CASES)))
+def test_poisoned_outputs_and_workspace(oracle, monkeypatch, tmp_path, case):
+    """workspace, bytes, end states and flags pre-filled with two different patterns: every byte of the result (the pad bits past
+    L in each frame's last byte included) is written by the call and equals the reference; then through the C ABI with only the
+    end states, only the flags and neither asked for, the same bytes"""
+    import torch
+
+    code, decode_type, family = POISON_CASES[case]
+    if family == GENERIC:
+        _no_compiler(monkeypatch, tmp_path)
+    pc, table, config = make_table_config(code, decode_type)
+    dec = BatchDecoder(table, config) if family == GENERIC else BatchDecoder(table, config, plan=PLAN_OF[family])
+    assert dec.plan == PLAN_OF[family] and ("GENERIC" in dec.plan_note) == (family == GENERIC), dec.plan_note
+    F, L, head, tail = (67, 41, 13, code.K + 2) if code.K < 10 else (5, 41, 13, code.K + 2)
+    nb = (L + 7) // 8
+    _, sym = tb_frames(code, pc, F, L, default_ebn0(code, decode_type), seed=31 + case)
+    d_sym = torch.from_numpy(sym).cuda()
+    want_out, want_ends, want_ok = tb_reference(oracle, code, oracle_cfg(decode_type, code.R), sym, L, head, tail)
+    need = dec.tail_biting_workspace_bytes(F, L, head, tail)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    out = torch.empty((F, nb), dtype=torch.uint8, device="cuda")
+    ends = torch.empty(F, dtype=torch.int32, device="cuda")
+    ok = torch.empty(F, dtype=torch.uint8, device="cuda")
+    results = []
+    for pattern in (0xFF, 0x5A):
+        for t in (ws, out, ok):
+            t.fill_(pattern)
+        ends.view(torch.uint8).fill_(pattern)
+        dec.decode_tail_biting(d_sym, L, head, tail, out=out, end_state_out=ends, ok_out=ok, workspace=ws)
+        torch.cuda.synchronize()
+        got = (out.cpu().numpy(), ends.cpu().numpy().view(np.uint32), ok.cpu().numpy())
+        tag = (code.name, decode_type, family, hex(pattern))
+        assert np.array_equal(got[0], want_out), tag
+        assert np.array_equal(got[1], want_ends), tag
+        assert np.array_equal(got[2], want_ok), tag
+        results.append(got)
+    assert all(np.array_equal(a, b) for a, b in zip(*results))
+    lib, h = _lib.load(), dec._handle._h
+    p = lambda t: C.c_void_p(t.data_ptr())                                     # noqa: E731
+    for with_ends, with_ok in ((True, False), (False, True), (False, False)):
+        for t in (ws, out, ok):
+            t.fill_(0xC3)
+        ends.view(torch.uint8).fill_(0xC3)
+        rc = lib.vit_hip_decode_tail_biting_batch(h, p(d_sym), F, L, head, tail, p(ws), need, p(out),
+                                                  p(ends) if with_ends else None, p(ok) if with_ok else None, None)
+        assert rc == _lib.OK
+        torch.cuda.synchronize()
+        tag = (code.name, decode_type, family, with_ends, with_ok)
+        assert np.array_equal(out.cpu().numpy(), want_out), tag
+        if with_ends:
+            assert np.array_equal(ends.cpu().numpy().view(np.uint32), want_ends), tag
+        else:
+            assert torch.all(ends.view(torch.uint8) == 0xC3), tag             # not asked for: not written
+        if with_ok:
+            assert np.array_equal(ok.cpu().numpy(), want_ok), tag
+        else:
+            assert torch.all(ok == 0xC3), tag
+
+
+# ---- batches large enough for the gather's grid-stride loop (8192 blocks of 256 threads, 16 bytes each) ----------------------
+def _large_batch_check(oracle, code, decode_type, F, distinct, L, seed):
+    import torch
+
+    pc, table, config = make_table_config(code, decode_type)
+    dec = BatchDecoder(table, config)
+    head = tail = 8 * (code.K - 1)
+    chunks = -(-F * (head + L + tail) * code.R * pc.soft_bytes // 16)
+    assert chunks > 8192 * 256, chunks                        # the gather strides at least once
+    _, sym = tb_frames(code, pc, distinct, L, default_ebn0(code, decode_type), seed=seed)
+    d_sym = torch.from_numpy(sym).cuda().repeat(F // distinct, 1, 1).contiguous()
+    out, ends, ok = dec.decode_tail_biting(d_sym, L, end_state_out=True, ok_out=True)
+    torch.cuda.synchronize()
+    want_out, want_ends, want_ok = tb_reference(oracle, code, oracle_cfg(decode_type, code.R), sym, L)
+    src = np.arange(F) % distinct                              # frame f is a copy of source frame f mod distinct
+    got = out.cpu().numpy()
+    bad = np.flatnonzero((got != want_out[src]).any(axis=1))
+    assert bad.size == 0, f"{code.name}: bytes differ in {bad.size} of {F} frames, first {bad[0]}"
+    bad = np.flatnonzero(ends.cpu().numpy().view(np.uint32) != want_ends[src])
+    assert bad.size == 0, f"{code.name}: end states differ in {bad.size} of {F} frames, first {bad[0]}"
+    bad = np.flatnonzero(ok.cpu().numpy() != want_ok[src])
+    assert bad.size == 0, f"{code.name}: flags differ in {bad.size} of {F} frames, first {bad[0]}"
+
+
+def test_large_batch_soft16_every_frame(oracle):
+    """test_side_pass_overhead's batch -- LTE SOFT16, 65536 frames of 40 bits, 4096 distinct repeated -- frame by frame"""
+    _large_batch_check(oracle, COMMON_CODES[3], "SOFT16", 65536, 4096, 40, seed=5)
+
+
+def test_large_batch_int8_every_frame(oracle):
+    """DAB K7 R4 HARD8, 8192 frames of 1000 bits from 512 distinct: 2.2 M chunks of 16 int8 symbols"""
+    _large_batch_check(oracle, COMMON_CODES[4], "HARD8", 8192, 512, 1000, seed=6)

@@ -1,5 +1,6 @@
 """Tail-biting decoding without a GPU: the C ABI and C++ surfaces exist, the rule restated on the CPU checker decodes tail-biting
 codewords of every stock code, and its default extension (8*(K-1) steps each side) is as good as exact maximum likelihood."""
+import functools
 import os
 import subprocess
 
@@ -86,6 +87,67 @@ def test_default_extension_is_near_maximum_likelihood(oracle, ebn0):
     ocfg = pyoracle.stock_config(pyoracle.SOFT16, code.R)
     F, L = 600, 40
     bits, sym = tb_frames(code, pc, F, L, ebn0, seed=int(ebn0 * 100) + 7)
+    ml = ml_tail_biting(code, sym, L)
+    out, _, _ = tb_reference(oracle, code, ocfg, sym, L)
+    got = np.unpackbits(out, axis=1)[:, :L]
+    ml_errors = int((ml != bits).any(axis=1).sum())
+    tb_errors = int((got != bits).any(axis=1).sum())
+    assert ml_errors > 0, "the operating point must produce frame errors"
+    assert tb_errors <= 1.1 * ml_errors + 3, (tb_errors, ml_errors)
+
+
+def _sweep_codes():
+    """the reference's butterfly assumes every polynomial taps both the newest and the oldest bit (viterbi_branch_table.h: only the
+    K-2 middle bits are enumerated); sets that do not -- every K = 2 set -- decode some other trellis and only oracle parity holds.
+    Rate 1 neither: any symbol sequence is an error-free path from every start state, so the rule's choice among them is arbitrary."""
+    from tests.test_gpu_tail_biting import SWEEP
+
+    outer = lambda K, G: all(g & 1 and g >> (K - 1) & 1 for g in G)            # noqa: E731
+    return sorted({(K, R, tuple(G), t) for K, R, G, t, _ in SWEEP if outer(K, G) and R > 1})
+
+
+def _gf2_gcd(a, b):
+    while b:
+        while a and a.bit_length() >= b.bit_length():
+            a ^= b << (a.bit_length() - b.bit_length())
+        a, b = b, a
+    return a
+
+
+@pytest.mark.parametrize("K,R,G,decode_type", _sweep_codes(), ids=lambda x: x if isinstance(x, (int, str)) else None)
+def test_reference_restatement_noise_free_sweep_codes(oracle, K, R, G, decode_type):
+    """the codes of test_gpu_tail_biting.py::SWEEP (K = 3 .. 16, R = 2 .. 8, non-stock polynomials): noise-free tail-biting
+    codewords come back as the same codeword, and at L = 41 as the same bits where the code is not catastrophic (the K = 16 set's
+    polynomials share the factor 1 + x: a frame and its complement are one codeword)"""
+    from viterbidecodercpp_amd import Code
+
+    code = Code(f"K{K}R{R}", K, R, G)
+    pc = get_decoding_config(decode_type, R)
+    ocfg = oracle_cfg(decode_type, R)
+    F = 2 if K >= 14 else 6
+    for L in (K, 41):
+        bits, sym = tb_frames(code, pc, F, L, None, seed=L + 100 * K + R)
+        out, ends, ok = tb_reference(oracle, code, ocfg, sym, L)
+        got = np.unpackbits(out, axis=1)[:, :L]
+        assert np.array_equal(synth.encode_tail_biting_numpy(K, R, G, got), synth.encode_tail_biting_numpy(K, R, G, bits)), \
+            (code.name, decode_type, L)
+        if L > K and functools.reduce(_gf2_gcd, G) == 1:
+            assert np.array_equal(got, bits), (code.name, decode_type, L)
+        assert np.all(np.unpackbits(out, axis=1)[:, L:] == 0)
+        assert np.all(ok == 1)
+
+
+# small K: the default extension wraps round the frame several times, where a wrap-around mistake in the restatement would show.
+# (Much below L = 5 K the fixed-extension rule itself falls short of maximum likelihood -- its best path through the repeated
+# frame need not be tail-biting -- so this bound only holds from there on.)
+@pytest.mark.parametrize("code_id,L,ebn0", [(0, 24, 2.0), (0, 40, 2.0), (1, 24, 2.0), (1, 40, 2.0)])
+def test_small_k_is_near_maximum_likelihood(oracle, code_id, L, ebn0):
+    code = COMMON_CODES[code_id]
+    assert code.K <= 5
+    pc = get_decoding_config("SOFT16", code.R)
+    ocfg = pyoracle.stock_config(pyoracle.SOFT16, code.R)
+    F = 600
+    bits, sym = tb_frames(code, pc, F, L, ebn0, seed=10 * L + code.K)
     ml = ml_tail_biting(code, sym, L)
     out, _, _ = tb_reference(oracle, code, ocfg, sym, L)
     got = np.unpackbits(out, axis=1)[:, :L]

@@ -95,15 +95,19 @@ struct TbSelectArgs {
 // key is the smallest metric (unsigned) and, among equal metrics, the lowest state.  log2 N <= 15 and error_t <= 16 bits: 31 bits.
 template <typename error_t, int VB>
 __device__ inline uint32_t tb_min_key(const uint8_t* p, uint32_t first_state, uint32_t log2N) {
-    uint32_t w[VB / 4];
+    static_assert(VB == 16 || VB == 8 || VB == 4 || VB == 2, "one 16-, 8-, 4- or 2-byte load");
+    static_assert(VB >= (int)sizeof(error_t), "at least one state per lane");
+    uint32_t w[VB >= 4 ? VB / 4 : 1];
     if constexpr (VB == 16) {
         const uint4 x = *(const uint4*)p;
         w[0] = x.x; w[1] = x.y; w[2] = x.z; w[3] = x.w;
     } else if constexpr (VB == 8) {
         const uint2 x = *(const uint2*)p;
         w[0] = x.x; w[1] = x.y;
-    } else {
+    } else if constexpr (VB == 4) {
         w[0] = *(const uint32_t*)p;
+    } else {
+        w[0] = *(const uint16_t*)p;                      // K = 2 with 8-bit metrics: the frame's whole 2 bytes
     }
     constexpr int V = VB / (int)sizeof(error_t);
     uint32_t best = 0xFFFFFFFFu;
@@ -116,8 +120,9 @@ __device__ inline uint32_t tb_min_key(const uint8_t* p, uint32_t first_state, ui
     return best;
 }
 
-// K <= 9 (N <= 256): P = N * sizeof(error_t) / VB lanes per frame (P <= 32), each with VB contiguous bytes of metrics (one 16-, 8-
-// or 4-byte load); a wavefront serves 64 / P frames and reduces each group of P lanes with xor shuffles (the groups are aligned).
+// K <= 9 (N <= 256): P = N * sizeof(error_t) / VB lanes per frame (1 <= P <= 32), each with VB contiguous bytes of metrics (one
+// 16-, 8-, 4- or 2-byte load, never past its frame: VB = min(16, N * sizeof(error_t))); a wavefront serves 64 / P frames and
+// reduces each group of P lanes with xor shuffles (the groups are aligned).
 template <typename error_t, int VB>
 __global__ void __launch_bounds__(256) tb_select_small_kernel(TbSelectArgs a) {
     const uint32_t N = 1u << a.log2N;
@@ -218,23 +223,29 @@ inline int tb_launch_gather(int soft_bytes, const TbGatherArgs& a, hipStream_t s
 }
 
 inline int tb_launch_select(int error_bytes, const TbSelectArgs& a, hipStream_t st) {
+    // a shape no kernel below serves is refused, never launched
+    if ((error_bytes != 1 && error_bytes != 2) || a.log2N < 1 || a.log2N > 15) return -1;
     const uint32_t N = 1u << a.log2N;
     if (a.log2N >= 9) {
         if (error_bytes == 2) hipLaunchKernelGGL(tb_select_large_kernel<uint16_t>, dim3(a.frames), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(tb_select_large_kernel<uint8_t>, dim3(a.frames), dim3(256), 0, st, a);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    const uint32_t bytes = N * (uint32_t)error_bytes;                // 4 .. 512 per frame
-    const uint32_t vb = bytes >= 16 ? 16 : bytes;                     // 16, 8 or 4
+    const uint32_t bytes = N * (uint32_t)error_bytes;                // 2 .. 512 per frame
+    const uint32_t vb = bytes >= 16 ? 16 : bytes;                     // 16, 8, 4 or 2: P = bytes / vb >= 1 lanes per frame
     const uint64_t lanes = (uint64_t)a.frames * (bytes / vb);
     const unsigned blocks = tb_blocks(lanes, 0xFFFFFFFFull);
     if (error_bytes == 2) {
         if (vb == 16) hipLaunchKernelGGL((tb_select_small_kernel<uint16_t, 16>), dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tb_select_small_kernel<uint16_t, 8>), dim3(blocks), dim3(256), 0, st, a);
+        else if (vb == 8) hipLaunchKernelGGL((tb_select_small_kernel<uint16_t, 8>), dim3(blocks), dim3(256), 0, st, a);
+        else if (vb == 4) hipLaunchKernelGGL((tb_select_small_kernel<uint16_t, 4>), dim3(blocks), dim3(256), 0, st, a);
+        else return -1;
     } else {
         if (vb == 16) hipLaunchKernelGGL((tb_select_small_kernel<uint8_t, 16>), dim3(blocks), dim3(256), 0, st, a);
         else if (vb == 8) hipLaunchKernelGGL((tb_select_small_kernel<uint8_t, 8>), dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tb_select_small_kernel<uint8_t, 4>), dim3(blocks), dim3(256), 0, st, a);
+        else if (vb == 4) hipLaunchKernelGGL((tb_select_small_kernel<uint8_t, 4>), dim3(blocks), dim3(256), 0, st, a);
+        else if (vb == 2) hipLaunchKernelGGL((tb_select_small_kernel<uint8_t, 2>), dim3(blocks), dim3(256), 0, st, a);
+        else return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
