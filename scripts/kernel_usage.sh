@@ -1,7 +1,7 @@
 #!/bin/bash
-# scripts/kernel_usage.sh <reg id | vit> -- VGPRs / scratch / occupancy of every kernel of one translation unit
+# scripts/kernel_usage.sh <reg id | vit | vit_host | vit_tools> -- VGPRs / scratch / occupancy of every kernel of one translation unit
 cd "$(dirname "$0")/../viterbidecodercpp_amd/csrc"
-if [ "$1" = "vit" ]; then SRC=vit_hip.hip; DEF=""; else SRC=reg_inst.hip; DEF="-DVIT_REG_ID=$1"; fi
+case "$1" in vit) SRC=vit_hip.hip; DEF="";; vit_*) SRC=$1.hip; DEF="";; *) SRC=reg_inst.hip; DEF="-DVIT_REG_ID=$1";; esac
 hipcc -O3 -std=c++17 --offload-arch=gfx950 $DEF -S --cuda-device-only -Rpass-analysis=kernel-resource-usage -o /dev/null $SRC 2>&1 |
   python3 -c "
 import re,sys

@@ -11,4 +11,12 @@ struct DevConfig {
     int16_t high, low;
 };
 
+// the branch error of one symbol, shared by the LDS plan and the single-frame kernels
+__device__ __forceinline__ uint16_t abs_soft(int32_t expected, int32_t y) {
+    // const soft_t error = expected - sym; error_t(get_abs(error))   (viterbi_decoder_scalar.h:68-71, :155-159)
+    const int16_t d = (int16_t)(expected - y);
+    const int16_t n = (int16_t)(-(int32_t)d);
+    return (uint16_t)(d > 0 ? d : n);
+}
+
 }  // namespace vit

@@ -30,7 +30,6 @@
 #include <utility>
 
 #include "common.hpp"
-#include "kernels_lds.hpp"
 
 namespace vit {
 
@@ -650,60 +649,5 @@ __global__ void __launch_bounds__(192) one_frame7_kernel(OneFrameArgs a) {
 
 constexpr size_t one_chainback_lds_bytes() { return ((size_t)ONE_CB_CHUNK + 64 + 8) * 8 + ONE_CB_CHUNK / 8 + 8; }
 inline bool one_supported(int K, int R) { return K >= 2 && K <= 7 && R >= 1 && R <= 8; }
-
-template <int SHIFT>
-inline int one_launch_update(int R, const OneUpdateArgs& a, hipStream_t st) {
-    if (one_update7_supported(a.K, R)) {
-        switch (R) {
-            case 1: hipLaunchKernelGGL((one_update7_kernel<1, SHIFT>), dim3(1), dim3(192), 0, st, a); break;
-            case 2: hipLaunchKernelGGL((one_update7_kernel<2, SHIFT>), dim3(1), dim3(192), 0, st, a); break;
-            case 3: hipLaunchKernelGGL((one_update7_kernel<3, SHIFT>), dim3(1), dim3(192), 0, st, a); break;
-            default: hipLaunchKernelGGL((one_update7_kernel<4, SHIFT>), dim3(1), dim3(192), 0, st, a); break;
-        }
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    switch (R) {
-        case 1: hipLaunchKernelGGL((one_update_kernel<1, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((one_update_kernel<2, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((one_update_kernel<3, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((one_update_kernel<4, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 5: hipLaunchKernelGGL((one_update_kernel<5, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 6: hipLaunchKernelGGL((one_update_kernel<6, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 7: hipLaunchKernelGGL((one_update_kernel<7, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((one_update_kernel<8, SHIFT>), dim3(1), dim3(64), 0, st, a); break;
-        default: return -1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-template <int SHIFT>
-inline int one_launch_frame(int R, const OneFrameArgs& a, hipStream_t st) {
-    const size_t smem = a.do_chainback ? one_chainback_lds_bytes() : 0;
-#define VIT_ONE_FRAME_CASE(r)                                                                                                              \
-    case r:                                                                                                                                \
-        if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(one_frame_kernel<r, SHIFT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1; \
-        hipLaunchKernelGGL((one_frame_kernel<r, SHIFT>), dim3(1), dim3(64), smem, st, a);                                                  \
-        break;
-#define VIT_ONE_FRAME7_CASE(r)                                                                                                             \
-    case r:                                                                                                                                \
-        if (smem > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(one_frame7_kernel<r, SHIFT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1; \
-        hipLaunchKernelGGL((one_frame7_kernel<r, SHIFT>), dim3(1), dim3(192), smem, st, a);                                                \
-        break;
-    if (one_update7_supported(a.u.K, R)) {
-        switch (R) {
-            VIT_ONE_FRAME7_CASE(1) VIT_ONE_FRAME7_CASE(2) VIT_ONE_FRAME7_CASE(3) VIT_ONE_FRAME7_CASE(4)
-            default: return -1;
-        }
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-#undef VIT_ONE_FRAME7_CASE
-    switch (R) {
-        VIT_ONE_FRAME_CASE(1) VIT_ONE_FRAME_CASE(2) VIT_ONE_FRAME_CASE(3) VIT_ONE_FRAME_CASE(4)
-        VIT_ONE_FRAME_CASE(5) VIT_ONE_FRAME_CASE(6) VIT_ONE_FRAME_CASE(7) VIT_ONE_FRAME_CASE(8)
-        default: return -1;
-    }
-#undef VIT_ONE_FRAME_CASE
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 }  // namespace vit

@@ -1934,18 +1934,20 @@ constexpr int reg_update_min_waves() { return 2; }
 //   K = 9, R = 4 (CDMA 2000): 217 used with the sub-chunk branch-metric fetch (RegChunk; 368 allocated -- ONE wave per SIMD --
 //          with the whole-step double buffer);
 //   K = 7, R = 3 (LTE): 248 -> 240, no scratch.
-// (the attribute takes a literal, not a template-dependent value: the translation unit of the code sets it -- reg_inst.hip
-// with -DVIT_REG_ID=1, 3, 4, reg_jit.hpp for the run-time compiled codes of those geometries)
-#if !defined(VIT_REG_UPDATE_VGPR_CAP) && defined(VIT_REG_ID)
-#if VIT_REG_ID == 1 || VIT_REG_ID == 3 || VIT_REG_ID == 4
+// (the attribute takes a literal, not a template-dependent value, so the preprocessor applies the rule: a translation unit that
+// instantiates the update kernel of ONE code names that code's K and R in VIT_REG_TU_K / VIT_REG_TU_R before it includes this
+// header -- reg_inst.hip from the stock list of reg_plan.hpp, the run-time compiled unit of reg_jit.hpp literally)
+#define VIT_REG_UPDATE_IS_CAPPED(K, R) ((K) == 9 || ((K) == 7 && (R) == 3))
+#if defined(VIT_REG_TU_K) && VIT_REG_UPDATE_IS_CAPPED(VIT_REG_TU_K, VIT_REG_TU_R)
 #define VIT_REG_UPDATE_VGPR_CAP __attribute__((amdgpu_num_vgpr(120)))
-#endif
-#endif
-#ifndef VIT_REG_UPDATE_VGPR_CAP
+#else
 #define VIT_REG_UPDATE_VGPR_CAP
 #endif
 template <class SP, int SHIFT>
 __global__ void __launch_bounds__(64, reg_update_min_waves<SP>()) VIT_REG_UPDATE_VGPR_CAP reg_update_kernel(RegUpdateArgs a) {
+#ifdef VIT_REG_TU_K
+    static_assert(SP::K == VIT_REG_TU_K && SP::R == VIT_REG_TU_R, "the register cap above was chosen for another code");
+#endif
 #ifdef VIT_HIP_CLOCK_STAMPS
     const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1976,8 +1978,8 @@ VIT_DEV void reg_chainback_body(const RegChainbackArgs& a) {
 constexpr unsigned reg_chainback_dyn_lds_bytes(int K, int R, bool alt) {
     return (K == 9 && !alt) ? reg_cb_ring_lds_bytes(64, R) : (K == 7 && alt) ? reg_cb_ring_lds_bytes(16, R) : 0u;
 }
-template <class SP>
-constexpr unsigned reg_chainback_frames_per_block() { return (SP::NREG == 16 || SP::NREG == 64) && SP::LANE_BITS == 2 ? 128u : SP::LANE_BITS == 0 ? 64u : 32u; }
+// frames per block of a code's chainback kernel: the ring bodies (K = 7, 9) take 128, the one-lane body (K < 7) 64, the cooperative one 32
+constexpr unsigned reg_chainback_frames_per_block(int K) { return (K == 7 || K == 9) ? 128u : K < 7 ? 64u : 32u; }
 // (the K = 9 body's LDS ring -- 40 KiB per one-wave workgroup -- allows four of them per CU)
 template <class SP>
 constexpr int reg_chainback_min_waves() { return SP::NREG == 64 ? 1 : 2; }
@@ -2009,308 +2011,5 @@ template <class SP>
 __global__ void __launch_bounds__(64, reg_chainback_alt_min_waves<SP>()) reg_chainback_alt_kernel(RegChainbackArgs a) { reg_chainback_alt_body<SP>(a); }
 template <class SP>
 __global__ void reg_export_kernel(RegExportArgs a) { reg_export_body<SP>(a); }
-
-#ifndef VIT_REG_JIT_TU
-}  // namespace vit
-#include "kernel_desc.hpp"
-namespace vit {
-// ---- host side ----------------------------------------------------------------------------------------------------
-using Spec_K7R2 = RegSpec<7, 2, 109, 79, 0, 0>;             // Voyager          (common_codes.h:23)
-using Spec_K7R3 = RegSpec<7, 3, 91, 117, 121, 0>;           // LTE              (:24)
-using Spec_K7R4 = RegSpec<7, 4, 109, 79, 83, 109>;          // DAB Radio        (:25)
-using Spec_K9R2 = RegSpec<9, 2, 491, 369, 0, 0>;            // CDMA IS-95A      (:26)
-using Spec_K9R4 = RegSpec<9, 4, 501, 441, 331, 315>;        // CDMA 2000        (:27)
-using Spec_K3R2 = RegSpec<3, 2, 7, 5, 0, 0, 0>;             // Basic K=3        (:21)  all 4 states in one lane
-using Spec_K5R2 = RegSpec<5, 2, 23, 25, 0, 0, 0>;           // Basic K=5        (:22)  all 16 states in one lane
-
-// a run-time compiled instantiation (reg_jit.hpp): the same four kernels for polynomials that are not in the table above
-struct RegJitModule {
-    hipModule_t module = nullptr;
-    hipFunction_t update[2] = {nullptr, nullptr};   // [0] 16-bit, [1] 8-bit metrics/symbols
-    hipFunction_t resume[2] = {nullptr, nullptr};
-    hipFunction_t chainback = nullptr, export_ = nullptr;
-    hipFunction_t chainback_alt = nullptr;         // K = 7, 9: the alternative body (reg_chainback_alt_body)
-    unsigned chainback_frames_per_block = 32;
-    kd::Table kernels;                              // kernel descriptors of the module's code object (kernel_desc.hpp)
-};
-
-struct RegCode {
-    int id = -1;   // 0..6 in the order above; -1 with jit != nullptr for a run-time compiled code
-    int K = 0, R = 0;
-    int tile = 32; // frames per wavefront
-    uint32_t G[6] = {0, 0, 0, 0, 0, 0};
-    const RegJitModule* jit = nullptr;
-    bool generic = false;   // jit is the GENERIC code object of (K, R): the kernels read G from their arguments (RegSpec::GENERIC)
-};
-
-// (K, R) with a generic register-plan kernel: the LDS-ring geometries (K = 7: whole-step fetch, K = 8, 9: per sub-chunk) and, below K = 7,
-// the one-lane geometry with the pairs parked in LDS; whole patterns (R <= 4)
-inline bool reg_generic_supported(int K, int R) {
-    // (K = 6 at an odd rate unrolls an 80- to 240-step block: minutes of hipcc per object; K = 2: one butterfly, nothing to look up)
-    return K >= 3 && K <= 9 && R >= 1 && R <= 4 && !(K == 6 && (R & 1));
-}
-
-inline bool reg_code_supported(int K, int R) {
-    return (K == 7 && R >= 2 && R <= 4) || (K == 9 && (R == 2 || R == 4)) || ((K == 3 || K == 5) && R == 2);
-}
-
-inline bool reg_code_init(RegCode* rc, int K, int R, const uint32_t* G, const DevConfig&) {
-    struct Entry { int K, R; uint32_t G[4]; };
-    static const Entry table[7] = {{7, 2, {109, 79, 0, 0}}, {7, 3, {91, 117, 121, 0}}, {7, 4, {109, 79, 83, 109}},
-                                   {9, 2, {491, 369, 0, 0}}, {9, 4, {501, 441, 331, 315}},
-                                   {3, 2, {7, 5, 0, 0}}, {5, 2, {23, 25, 0, 0}}};
-    for (int id = 0; id < 7; ++id) {
-        if (table[id].K != K || table[id].R != R) continue;
-        bool same = true;
-        for (int i = 0; i < R; ++i) same = same && (table[id].G[i] == G[i]);
-        if (same) {
-            rc->id = id; rc->K = K; rc->R = R; rc->tile = K < 7 ? 128 : 32;
-            for (int i = 0; i < 4; ++i) rc->G[i] = table[id].G[i];
-            rc->G[4] = rc->G[5] = 0;
-            return true;
-        }
-    }
-    return false;
-}
-
-// host mirror of RegSpec's geometry: lane bits, registers per lane, decision dwords per step, steps per 16-byte row
-inline int reg_lane_bits(int K) { return K >= 7 ? 2 : 0; }
-inline size_t reg_steps_per_row(int K) {
-    const size_t nreg = (size_t)1 << (K - 1 - reg_lane_bits(K));
-    const size_t dw = nreg >= 16 ? nreg / 16 : 1;
-    return 4 / dw;
-}
-inline size_t reg_groups(const RegCode& rc, size_t L) {
-    const size_t S = L + (size_t)rc.K - 1;
-    const size_t sps = reg_steps_per_row(rc.K);
-    return (S + sps - 1) / sps;
-}
-inline size_t reg_tiles(const RegCode& rc, size_t frames) { return (frames + (size_t)rc.tile - 1) / (size_t)rc.tile; }
-inline size_t reg_workspace_bytes(const RegCode& rc, size_t frames, size_t L) {
-    return reg_tiles(rc, frames) * reg_groups(rc, L) * 1024;
-}
-
-// The kernels are instantiated one code per translation unit (reg_inst.hip, compiled with -DVIT_REG_ID=0..4) so that the
-// heavy unrolled bodies build in parallel; these are the per-code launchers those units define.
-template <int ID> struct RegSpecOf;
-template <> struct RegSpecOf<0> { using type = Spec_K7R2; };
-template <> struct RegSpecOf<1> { using type = Spec_K7R3; };
-template <> struct RegSpecOf<2> { using type = Spec_K7R4; };
-template <> struct RegSpecOf<3> { using type = Spec_K9R2; };
-template <> struct RegSpecOf<4> { using type = Spec_K9R4; };
-template <> struct RegSpecOf<5> { using type = Spec_K3R2; };
-template <> struct RegSpecOf<6> { using type = Spec_K5R2; };
-
-template <int ID> int reg_launch_update(int shift, const RegUpdateArgs& a, unsigned tiles, hipStream_t st);
-template <int ID> int reg_launch_chainback(const RegChainbackArgs& a, unsigned tiles, hipStream_t st, bool coop);
-template <int ID> int reg_launch_export(const RegExportArgs& a, unsigned blocks, hipStream_t st);
-
-#ifdef VIT_REG_ID
-template <> int reg_launch_update<VIT_REG_ID>(int shift, const RegUpdateArgs& a, unsigned tiles, hipStream_t st) {
-    using SP = RegSpecOf<VIT_REG_ID>::type;
-    if (a.metrics_in) {
-        if (shift) hipLaunchKernelGGL((reg_resume_kernel<SP, 8>), dim3(tiles), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((reg_resume_kernel<SP, 0>), dim3(tiles), dim3(64), 0, st, a);
-    } else {
-        if (shift) hipLaunchKernelGGL((reg_update_kernel<SP, 8>), dim3(tiles), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((reg_update_kernel<SP, 0>), dim3(tiles), dim3(64), 0, st, a);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-template <> int reg_launch_chainback<VIT_REG_ID>(const RegChainbackArgs& a, unsigned tiles, hipStream_t st, bool coop) {
-    using SP = RegSpecOf<VIT_REG_ID>::type;
-    constexpr unsigned FPB = reg_chainback_frames_per_block<SP>();
-    if (coop && SP::NREG == 64) hipLaunchKernelGGL(reg_chainback_alt_kernel<SP>, dim3(tiles), dim3(64), 0, st, a);
-    else if (coop && SP::NREG == 16 && SP::LANE_BITS == 2) hipLaunchKernelGGL(reg_chainback_alt_kernel<SP>, dim3((a.frames + 127) / 128), dim3(64), reg_chainback_dyn_lds_bytes(SP::K, SP::R, true), st, a);
-    else hipLaunchKernelGGL(reg_chainback_kernel<SP>, dim3((a.frames + FPB - 1) / FPB), dim3(64), reg_chainback_dyn_lds_bytes(SP::K, SP::R, false), st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-template <> int reg_launch_export<VIT_REG_ID>(const RegExportArgs& a, unsigned blocks, hipStream_t st) {
-    using SP = RegSpecOf<VIT_REG_ID>::type;
-    hipLaunchKernelGGL(reg_export_kernel<SP>, dim3(blocks), dim3(256), 0, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-#else
-template <> int reg_launch_update<0>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_update<1>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_update<2>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_update<3>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_update<4>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_update<5>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_update<6>(int, const RegUpdateArgs&, unsigned, hipStream_t);
-template <> int reg_launch_chainback<0>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_chainback<1>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_chainback<2>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_chainback<3>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_chainback<4>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_chainback<5>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_chainback<6>(const RegChainbackArgs&, unsigned, hipStream_t, bool);
-template <> int reg_launch_export<0>(const RegExportArgs&, unsigned, hipStream_t);
-template <> int reg_launch_export<1>(const RegExportArgs&, unsigned, hipStream_t);
-template <> int reg_launch_export<2>(const RegExportArgs&, unsigned, hipStream_t);
-template <> int reg_launch_export<3>(const RegExportArgs&, unsigned, hipStream_t);
-template <> int reg_launch_export<4>(const RegExportArgs&, unsigned, hipStream_t);
-template <> int reg_launch_export<5>(const RegExportArgs&, unsigned, hipStream_t);
-template <> int reg_launch_export<6>(const RegExportArgs&, unsigned, hipStream_t);
-
-// ---- which kernels can share a SIMD: read from the kernel DESCRIPTORS (kernel_desc.hpp), the numbers the wave launcher uses ----
-// (hipFuncGetAttributes().numRegs is the count the code USES; hipcc pads the allocation of kernels whose static LDS limits their
-// occupancy -- round 3's K = 9 chainback used 22 registers and allocated 264)
-enum RegKernelKind { REG_KERNEL_UPDATE = 0, REG_KERNEL_CHAINBACK = 1, REG_KERNEL_CHAINBACK_ALT = 2, REG_KERNEL_RESUME = 3 };
-inline bool reg_kernel_resources(const RegCode& rc, int shift, int kind, kd::KernelResources* out, unsigned* dyn_lds_bytes = nullptr) {
-    if (dyn_lds_bytes) *dyn_lds_bytes = kind == REG_KERNEL_CHAINBACK ? reg_chainback_dyn_lds_bytes(rc.K, rc.R, false)
-                                      : kind == REG_KERNEL_CHAINBACK_ALT ? reg_chainback_dyn_lds_bytes(rc.K, rc.R, true) : 0u;
-    const kd::KernelResources* r = nullptr;
-    if (rc.jit) {
-        const char* name = kind == REG_KERNEL_UPDATE ? (shift ? "vit_jit_update_8" : "vit_jit_update_16")
-                         : kind == REG_KERNEL_RESUME ? (shift ? "vit_jit_resume_8" : "vit_jit_resume_16")
-                         : kind == REG_KERNEL_CHAINBACK ? "vit_jit_chainback" : "vit_jit_chainback_alt";
-        for (const auto& e : rc.jit->kernels)
-            if (e.first == name) r = &e.second;
-    } else {
-        // Itanium mangling of vit::<kernel><RegSpec<K, R, G0, G1, G2, G3, LANE_BITS, G4, G5>[, SHIFT]>(Args)
-        char spec[128], tail[48];
-        snprintf(spec, sizeof(spec), "7RegSpecILi%dELi%dELj%uELj%uELj%uELj%uELi%dELj%uELj%uEEE", rc.K, rc.R, rc.G[0], rc.G[1], rc.G[2], rc.G[3],
-                 reg_lane_bits(rc.K), rc.G[4], rc.G[5]);
-        snprintf(tail, sizeof(tail), "ELi%dEEEvNS_13RegUpdateArgsE", shift ? 8 : 0);
-        std::vector<std::string> frag;
-        if (kind == REG_KERNEL_UPDATE) frag = {"17reg_update_kernelI", spec, tail};
-        else if (kind == REG_KERNEL_RESUME) frag = {"17reg_resume_kernelI", spec, tail};
-        else if (kind == REG_KERNEL_CHAINBACK) frag = {"20reg_chainback_kernelI", spec};
-        else frag = {"24reg_chainback_alt_kernelI", spec};
-        r = kd::find(kd::own_library(), frag);
-    }
-    if (!r) return false;
-    *out = *r;
-    return true;
-}
-
-constexpr unsigned SIMD_VGPRS = 512, CU_LDS_BYTES = 160 * 1024;
-// can `n_update` update waves and one chainback wave of this code share a SIMD: registers (the descriptors' allocations), and per
-// CU the LDS of 4 n_update update waves plus two chainback workgroups (a 65536-frame batch is 512 of them on 256 CUs)?  When they
-// cannot (K = 9, R = 4: one update wave allocates 360 registers), the chainback of a batch only runs in the gaps between update
-// kernels, and the pipeline does better feeding the SIMDs half-size sub-batches from two streams.  Descriptors that cannot be
-// read (the library file moved away under the process) answer "no": the conservative schedule.
-inline bool reg_chainback_fits_beside_updates(const RegCode& rc, int shift, int n_update, bool alt_chainback = false) {
-    kd::KernelResources u, c;
-    unsigned dyn = 0;
-    if (!reg_kernel_resources(rc, shift, REG_KERNEL_UPDATE, &u) ||
-        !reg_kernel_resources(rc, shift, alt_chainback ? REG_KERNEL_CHAINBACK_ALT : REG_KERNEL_CHAINBACK, &c, &dyn))
-        return false;
-    if ((unsigned)n_update * u.vgpr_alloc + c.vgpr_alloc > SIMD_VGPRS) return false;
-    return 4u * (unsigned)n_update * u.lds_static_bytes + 2u * (c.lds_static_bytes + dyn) <= CU_LDS_BYTES;
-}
-inline bool reg_chainback_fits_beside_two_updates(const RegCode& rc, int shift) { return reg_chainback_fits_beside_updates(rc, shift, 2); }
-
-inline int reg_jit_launch(hipFunction_t fn, const void* args, size_t args_bytes, unsigned grid, unsigned block, hipStream_t st,
-                          unsigned dyn_lds_bytes = 0) {
-    void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void*>(args), HIP_LAUNCH_PARAM_BUFFER_SIZE, &args_bytes,
-                      HIP_LAUNCH_PARAM_END};
-    return hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, dyn_lds_bytes, st, nullptr, config) == hipSuccess ? 0 : -1;
-}
-
-// steps [first_step, first_step + n_steps) of every frame.  d_metrics_in == null: reset(start_state) (first_step must be 0);
-// else resume from those metrics.  sym_stride: soft_t elements between the chunks of consecutive frames.
-inline int reg_update(const RegCode& rc, const DevConfig& cfg, int shift, const void* d_symbols, size_t sym_stride, size_t frames,
-                      size_t first_step, size_t n_steps, size_t L, void* d_ws, const void* d_metrics_in, void* d_metrics,
-                      uint64_t* d_renorm, const uint32_t* d_start, hipStream_t st) {
-    if (frames == 0 || n_steps == 0) return 0;
-    RegUpdateArgs a{};
-    a.symbols = (const uint8_t*)d_symbols;
-    a.sym_frame_stride_bytes = sym_stride * (shift ? 1 : 2);
-    // per-lane 32-bit buffer offsets; a resumed call's look-ahead may form slightly negative offsets (see reg_update_body):
-    // they must stay distinguishable from valid ones (sign bit) and out of the descriptor's range
-    if (a.sym_frame_stride_bytes * (size_t)rc.tile + 65536 >= (d_metrics_in ? 0x7FFF0000ull : 0xFFFF0000ull)) return -2;
-    // the last frame's chunk ends n_steps into its stride
-    a.sym_total_bytes = (frames - 1) * a.sym_frame_stride_bytes + n_steps * (size_t)rc.R * (shift ? 1 : 2);
-    a.ws = (uint4*)d_ws;
-    a.ws_tile_stride = reg_groups(rc, L) * 64;
-    a.metrics_out = d_metrics;
-    a.renorm_sum = d_renorm;
-    a.start_state = d_start;
-    a.metrics_in = d_metrics_in;
-    a.frames = (u32)frames;
-    a.t_begin = (u32)first_step;
-    a.t_end = (u32)(first_step + n_steps);
-    a.cfg = cfg;
-    for (int i = 0; i < 6; ++i) a.gen_G[i] = rc.G[i];
-#ifdef VIT_HIP_CLOCK_STAMPS
-    a.stamps = g_clock_stamps;
-#endif
-    const unsigned tiles = (unsigned)reg_tiles(rc, frames);
-    if (rc.jit) return reg_jit_launch((d_metrics_in ? rc.jit->resume : rc.jit->update)[shift ? 1 : 0], &a, sizeof(a), tiles, 64, st);
-    switch (rc.id) {
-        case 0: return reg_launch_update<0>(shift, a, tiles, st);
-        case 1: return reg_launch_update<1>(shift, a, tiles, st);
-        case 2: return reg_launch_update<2>(shift, a, tiles, st);
-        case 3: return reg_launch_update<3>(shift, a, tiles, st);
-        case 4: return reg_launch_update<4>(shift, a, tiles, st);
-        case 5: return reg_launch_update<5>(shift, a, tiles, st);
-        case 6: return reg_launch_update<6>(shift, a, tiles, st);
-        default: return -1;
-    }
-}
-
-// `prefer_alt`: launch the code's OTHER chainback kernel (K = 7: the LDS-ring body, 32 registers -- what the pipeline asks for
-// when the chainback shares SIMDs with update waves; K = 9: the cooperative body): vit_hip_chainback_batch_ex picks it.
-inline int reg_chainback(const RegCode& rc, const void* d_ws, size_t frames, size_t L, uint8_t* d_out, const uint32_t* d_end,
-                         hipStream_t st, unsigned wave_priority = 0, bool prefer_alt = false) {
-    if (frames == 0 || L == 0) return 0;
-    RegChainbackArgs a{};
-    a.ws = (const uint4*)d_ws;
-    a.ws_tile_stride = reg_groups(rc, L) * 64;
-    a.out = d_out;
-    a.end_state = d_end;
-    a.frames = (u32)frames;
-    a.L = (u32)L;
-    a.wave_priority = wave_priority;
-    const unsigned tiles = (unsigned)reg_tiles(rc, frames);
-    // K = 7, 9: the other chainback kernel of the code (reg_chainback_alt_body)
-    bool coop = prefer_alt && (rc.K == 9 || rc.K == 7);
-#ifdef VIT_HIP_EXPERIMENTS
-    if (const char* e = getenv("VIT_HIP_CHAINBACK_ALT")) coop = (rc.K == 9 || rc.K == 7) && *e == '1';   // A/B builds only
-#endif
-    if (rc.jit) {
-        if (coop && rc.jit->chainback_alt)
-            return reg_jit_launch(rc.jit->chainback_alt, &a, sizeof(a), rc.K == 9 ? tiles : (unsigned)((frames + 127) / 128), 64, st,
-                                  reg_chainback_dyn_lds_bytes(rc.K, rc.R, true));
-        const unsigned fpb = rc.jit->chainback_frames_per_block;
-        return reg_jit_launch(rc.jit->chainback, &a, sizeof(a), (unsigned)((frames + fpb - 1) / fpb), 64, st,
-                              reg_chainback_dyn_lds_bytes(rc.K, rc.R, false));
-    }
-    switch (rc.id) {
-        case 0: return reg_launch_chainback<0>(a, tiles, st, coop);
-        case 1: return reg_launch_chainback<1>(a, tiles, st, coop);
-        case 2: return reg_launch_chainback<2>(a, tiles, st, coop);
-        case 3: return reg_launch_chainback<3>(a, tiles, st, coop);
-        case 4: return reg_launch_chainback<4>(a, tiles, st, coop);
-        case 5: return reg_launch_chainback<5>(a, tiles, st, coop);
-        case 6: return reg_launch_chainback<6>(a, tiles, st, coop);
-        default: return -1;
-    }
-}
-
-inline int reg_export(const RegCode& rc, const void* d_ws, size_t frames, size_t n_steps, size_t L, uint64_t* d_out,
-                      hipStream_t st) {
-    if (frames == 0 || n_steps == 0) return 0;
-    RegExportArgs a{};
-    a.ws32 = (const u32*)d_ws;
-    a.ws_tile_stride = reg_groups(rc, L) * 64;
-    a.out = d_out;
-    a.frames = (u32)frames;
-    a.n_steps = (u32)n_steps;
-    const size_t W = rc.K >= 7 ? (size_t)1 << (rc.K - 7) : 1;
-    const size_t total = frames * n_steps * W;
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (rc.jit) return reg_jit_launch(rc.jit->export_, &a, sizeof(a), blocks, 256, st);
-    switch (rc.K) {
-        case 9: return reg_launch_export<3>(a, blocks, st);
-        case 3: return reg_launch_export<5>(a, blocks, st);
-        case 5: return reg_launch_export<6>(a, blocks, st);
-        default: return reg_launch_export<0>(a, blocks, st);
-    }
-}
-#endif  // VIT_REG_ID
-#endif  // VIT_REG_JIT_TU
 
 }  // namespace vit

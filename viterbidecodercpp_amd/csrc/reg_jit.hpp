@@ -1,7 +1,7 @@
 // reg_jit.hpp -- run-time instantiation of PLAN_REG for polynomials outside the ahead-of-time table.
 //
 // PLAN_REG's branch-pattern bookkeeping is compile-time (kernels_reg.hpp: RegSpec<K,R,G...>), so a new code needs a new
-// instantiation.  On first use we write a four-kernel translation unit that includes kernels_reg.hpp with the caller's
+// instantiation.  On first use we write a four-kernel translation unit that includes kernels_reg.hpp (and nothing else) with the caller's
 // polynomials, compile it with `hipcc --genco` for gfx950 (about as long as one of the ahead-of-time units: 10-40 s),
 // keep the code object in a disk cache and load it with hipModuleLoad.  Later handles -- and later processes -- reuse it.
 //   cache directory : $VIT_HIP_CACHE_DIR, else $XDG_CACHE_HOME/vit_hip, else $HOME/.cache/vit_hip, else /tmp/vit_hip_cache-<uid>;
@@ -29,7 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "kernels_reg.hpp"
+#include "reg_plan.hpp"
 
 extern char** environ;
 
@@ -153,10 +153,10 @@ inline std::string reg_jit_object_name(int K, int R, const uint32_t* G, int shif
     using namespace jit_detail;
     const std::string src_dir = this_library_dir() + "/csrc";
     uint64_t h = 1469598103934665603ull;
+    // exactly what the unit reg_jit_compile writes can include: the device code, not the host side of the plan (reg_plan.hpp)
     h = fnv1a_file(src_dir + "/kernels_reg.hpp", h);
     h = fnv1a_file(src_dir + "/common.hpp", h);
     if (h == 1469598103934665603ull) { err = "kernel sources not found next to the library (" + src_dir + ")"; return std::string(); }
-    h = fnv1a_file(src_dir + "/kernel_desc.hpp", h);
     std::ostringstream key;
     key << "reg_K" << K << "R" << R;
     for (int i = 0; i < 6; ++i) key << "_" << (i < R ? G[i] : 0u);
@@ -169,7 +169,6 @@ inline std::string reg_jit_object_name(int K, int R, const uint32_t* G, int shif
 inline bool reg_jit_compile(int K, int R, const uint32_t* G, int shift, const std::string& hsaco, std::string& err) {
     using namespace jit_detail;
     if (!reg_jit_supported(K, R)) { err = "PLAN_REG run-time instantiation serves K = 2..9 with R <= 6"; return false; }
-    const int lane_bits = K >= 7 ? 2 : 0;
     const std::string src_dir = this_library_dir() + "/csrc";
     const char* cc_env = getenv("VIT_HIP_HIPCC");
     const std::string hipcc = cc_env && *cc_env ? cc_env : "/opt/rocm/bin/hipcc";
@@ -178,12 +177,11 @@ inline bool reg_jit_compile(int K, int R, const uint32_t* G, int shift, const st
     const std::string src = base + "." + std::to_string((long)getpid()) + ".hip";
     {
         std::ofstream f(src);
-        f << "#define VIT_REG_JIT_TU 1\n";
-        if (K == 9 || (K == 7 && R == 3)) f << "#define VIT_REG_UPDATE_VGPR_CAP __attribute__((amdgpu_num_vgpr(120)))\n";   // kernels_reg.hpp, reg_update_kernel
-        f << "#include \"" << src_dir << "/kernels_reg.hpp\"\n"
+        f << "#define VIT_REG_TU_K " << K << "\n#define VIT_REG_TU_R " << R << "\n"       // kernels_reg.hpp: VIT_REG_UPDATE_VGPR_CAP
+          << "#include \"" << src_dir << "/kernels_reg.hpp\"\n"
           << "using SP = vit::RegSpec<" << K << ", " << R;
         for (int i = 0; i < 4; ++i) f << ", " << (i < R ? G[i] : 0u) << "u";
-        f << ", " << lane_bits << ", " << (4 < R ? G[4] : 0u) << "u, " << (5 < R ? G[5] : 0u) << "u>;\n"
+        f << ", " << reg_lane_bits(K) << ", " << (4 < R ? G[4] : 0u) << "u, " << (5 < R ? G[5] : 0u) << "u>;\n"
           << "extern \"C\" __global__ void __launch_bounds__(64, vit::reg_update_min_waves<SP>()) VIT_REG_UPDATE_VGPR_CAP vit_jit_update_" << (shift ? 8 : 16)
           << "(vit::RegUpdateArgs a) { vit::reg_update_body<SP, " << (shift ? 8 : 0) << ", false>(a); }\n"
           << "extern \"C\" __global__ void __launch_bounds__(64, 1) vit_jit_resume_" << (shift ? 8 : 16) << "(vit::RegUpdateArgs a) { vit::reg_update_body<SP, "
@@ -216,7 +214,6 @@ inline const RegJitModule* reg_jit_get(int K, int R, const uint32_t* G, int shif
                                        std::string* origin = nullptr) {
     using namespace jit_detail;
     if (!reg_jit_supported(K, R)) { err = "PLAN_REG run-time instantiation serves K = 2..9 with R <= 6"; return nullptr; }
-    const int lane_bits = K >= 7 ? 2 : 0;
     const std::string name = reg_jit_object_name(K, R, G, shift, err);
     if (name.empty()) return nullptr;
     std::lock_guard<std::mutex> lock(mutex());
@@ -255,7 +252,6 @@ inline const RegJitModule* reg_jit_get(int K, int R, const uint32_t* G, int shif
         delete m;
         return nullptr;
     }
-    m->chainback_frames_per_block = (K == 7 || K == 9) ? 128u : lane_bits == 0 ? 64u : 32u;
     (void)kd::parse_file(hsaco, m->kernels);           // an unreadable table only makes the pipeline pick its conservative schedule
     if ((K == 9 || K == 7) && hipModuleGetFunction(&m->chainback_alt, m->module, "vit_jit_chainback_alt") != hipSuccess) m->chainback_alt = nullptr;
     modules()[mkey] = m;
