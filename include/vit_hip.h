@@ -31,6 +31,9 @@
  *   vit_hip_decode_tail_biting_batch  tail-biting frames (no tail, the encoder starts in the state its last K-1 bits leave):
  *                             no reference counterpart -- the reference decodes terminated frames only; this call is written
  *                             in terms of its reset / update / chainback (rule below), with _tail_biting_workspace_bytes
+ *   vit_hip_decode_stream     one long unterminated stream as overlapped windows: no reference counterpart either (the reference
+ *                             decodes one terminated frame per Core); written in terms of its reset / update / chainback (rule
+ *                             below), with vit_hip_stream_workspace_bytes
  *   vit_hip_broadcast_table   "Branch table can be shared between multiple decoders"   README.md:14,
  *                             viterbi_branch_table.h:17-18, one decoder per worker examples/run_benchmark.cpp:193-197:
  *                             here the workers are GPUs and the table travels once over RCCL/xGMI
@@ -360,6 +363,54 @@ size_t vit_hip_tail_biting_workspace_bytes(vit_hip_handle h, size_t frames, size
 int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, size_t frames, size_t L, size_t head,
                                      size_t tail, void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out,
                                      uint32_t* d_end_state_out, uint8_t* d_tail_biting_ok, vit_hip_stream_t stream);
+
+/* ---- one long unterminated stream, decoded as overlapped windows ("sliding-window Viterbi with fixed extension", one pass) -------
+ * A receiver's continuous convolutionally coded stream has no tail between blocks.  One call decodes one SEGMENT of T trellis steps
+ * of it as a batch of overlapping windows on the plan's own update / chainback kernels.  Rule, bit-exact, in terms of the
+ * reference's reset / update / chainback, with window W, extension head / tail and flags:
+ *   - VIT_HIP_STREAM_BEGIN: step 0 is the encoder's start in state 0 and bits are emitted from bit 0.  Without it the first `head`
+ *     steps are lead-in only (the previous call emitted them);
+ *   - VIT_HIP_STREAM_END: the last K-1 steps are the zero tail, the end state is 0 and bits are emitted up to T-(K-1).  Without it
+ *     the last `tail` steps are look-ahead only: the caller presents them again, with `head` steps before them, as the start of the
+ *     next segment (the next segment starts at step T - tail - head of this one);
+ *   - emitted range [a, b): a = BEGIN ? 0 : head, b = END ? T-(K-1) : T-tail; n_out = b - a bits, MSB-first, ceil(n_out/8) bytes,
+ *     pad bits 0;
+ *   - windows: n = max(1, floor((b - head) / W)).  Window i runs steps [i W, i W + head + W + tail) for i < n-1; the last window
+ *     runs [(n-1) W, T): it absorbs the remainder and is between one and just under two windows long.  When b - head is a multiple
+ *     of W and END is clear all n windows have the same length: a caller that sizes its segments T = head + n W + tail gets one
+ *     uniform batch (recommended: the longer last window is a launch of one frame);
+ *   - bits: window i emits bits [head + i W, head + (i+1) W) of the segment; window 0 under BEGIN also [0, head); the last window up
+ *     to b;
+ *   - start metrics: window 0 under BEGIN starts from reset(0); every other window with every state at initial_start_error (the
+ *     tail-biting start);
+ *   - end state: the last window under END ends in state 0; every other window in the state of smallest final metric, compared as
+ *     unsigned error_t, the lowest state on a tie;
+ *   - decode: each window runs update() over its steps, then chainback() over steps - (K-1) bits from its end state; its share of
+ *     the output is the bit range above, relative to its first step.
+ * Arguments: head, tail >= K-1; W >= 8, W >= head, W >= tail (so that every window but the last lies inside the segment under END);
+ * b > a; T >= head + tail + (BEGIN ? 0 : 1); T < 2^31 - 16 and (127 W + head + W + tail) * R * sizeof(soft_t) < 2^31 - 2^17 (the
+ * launchers' 32-bit counters); no other flag bit.  Everything else is VIT_HIP_ERR_INVALID_ARG and nothing is launched.
+ * 8*(K-1) for head and tail and W = 1024 are the defaults of the C++ and Python layers.
+ *   d_symbols    [T][R] soft_t, contiguous: the windows are read in place at a stride of W steps (no gather, no copy)
+ *   d_workspace  >= vit_hip_stream_workspace_bytes(h, T, W, head, tail, flags) bytes, 256-byte aligned (VIT_HIP_ERR_WORKSPACE
+ *                otherwise); it holds, each part 256-byte aligned: the decision workspaces of the uniform windows and of the
+ *                longer last window, their [n][N] metrics, end states and chainback bytes
+ *   d_bytes_out  [ceil(n_out/8)]
+ *   n_bits_out   host, may be NULL: receives n_out (known from the arguments alone: written before the work has run)
+ * A batch call like the others: it only enqueues on `stream` -- FIVE launches when every window has the same length (start
+ * metrics, update, end-state select, chainback, stitch), up to EIGHT otherwise (a second update, select and chainback for the
+ * longer last window; no select for a window that ends in state 0) -- with no allocation and no synchronisation, and can be
+ * captured into a hipGraph; several may be in flight on one handle, each with its own workspace.  ONE stream per call: a caller
+ * with several streams issues several calls (the update kernels take one frame stride; a second level would mean changing them).
+ * Punctured streams need nothing new: vit_hip_depuncture_batch with `frames` = the number of puncturing periods turns the received
+ * stream into the contiguous [T][R] buffer this call reads.
+ * vit_hip_stream_workspace_bytes returns 0 for arguments the decode call rejects. */
+#define VIT_HIP_STREAM_BEGIN 1u
+#define VIT_HIP_STREAM_END 2u
+size_t vit_hip_stream_workspace_bytes(vit_hip_handle h, size_t T, size_t W, size_t head, size_t tail, unsigned flags);
+int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
+                          void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, size_t* n_bits_out,
+                          vit_hip_stream_t stream);
 
 /* ---- multi-GPU set-up for C/C++ hosts ----------------------------------------------------------------------------------- */
 

@@ -84,6 +84,21 @@ public:
                                                workspace_size, d_bytes_out, d_end_state_out, d_tail_biting_ok, stream),
               "vit_hip_decode_tail_biting_batch");
     }
+    // one long unterminated stream (vit_hip_decode_stream): d_symbols [steps][R], one segment per call, decoded as overlapped
+    // windows of `window` steps (0: 1024) with `head` steps of lead-in and `tail` of look-ahead (0: the default 8*(K-1)); begin /
+    // end: the segment holds the encoder's start / the zero tail.  Returns the number of bits written to d_bytes_out, MSB-first.
+    size_t stream_workspace_bytes(size_t steps, bool begin, bool end, size_t window = 0, size_t head = 0, size_t tail = 0) const {
+        return vit_hip_stream_workspace_bytes(m_hip, steps, window ? window : 1024, extension(head), extension(tail),
+                                              stream_flags(begin, end));
+    }
+    size_t decode_stream(const soft_t* d_symbols, size_t steps, bool begin, bool end, void* d_workspace, size_t workspace_size,
+                         uint8_t* d_bytes_out, size_t window = 0, size_t head = 0, size_t tail = 0, void* stream = nullptr) {
+        size_t n_bits = 0;
+        check(vit_hip_decode_stream(m_hip, d_symbols, steps, window ? window : 1024, extension(head), extension(tail),
+                                    stream_flags(begin, end), d_workspace, workspace_size, d_bytes_out, &n_bits, stream),
+              "vit_hip_decode_stream");
+        return n_bits;
+    }
     // test / measurement harness on the device: the BER harness's frame generator (examples/run_snr_ber.cpp:311-359) and
     // get_total_bit_errors (examples/helpers/test_helpers.h:95-104)
     void synth(size_t frames, size_t total_bits, uint64_t seed, uint64_t first_frame, float ebn0_db, bool noise_free,
@@ -109,6 +124,7 @@ public:
 
 private:
     static size_t extension(size_t steps) { return steps ? steps : 8 * (K - 1); }
+    static unsigned stream_flags(bool begin, bool end) { return (begin ? VIT_HIP_STREAM_BEGIN : 0u) | (end ? VIT_HIP_STREAM_END : 0u); }
     static void check(int rc, const char* what) {
         if (rc != VIT_HIP_OK) {
             fprintf(stderr, "viterbi_hip: %s failed (%d): %s\n", what, rc, vit_hip_last_error());

@@ -30,6 +30,7 @@ EXPORTS = [
     "vit_hip_chainback_batch_ex", "vit_hip_pipeline_create_ex", "vit_hip_pipeline_get_schedule_v2", "vit_hip_plan_note",
     "vit_hip_precompile", "vit_hip_update_host_lazy", "vit_hip_chainback_host_lazy", "vit_hip_fetch_decisions_host",
     "vit_hip_tail_biting_workspace_bytes", "vit_hip_decode_tail_biting_batch",
+    "vit_hip_stream_workspace_bytes", "vit_hip_decode_stream",
 ]
 
 
@@ -65,6 +66,7 @@ class VitHipKernelResources(C.Structure):
 
 
 KERNEL_UPDATE, KERNEL_CHAINBACK, KERNEL_CHAINBACK_ALT, KERNEL_RESUME = 0, 1, 2, 3
+STREAM_BEGIN, STREAM_END = 1, 2
 
 
 class VitHipError(RuntimeError):
@@ -120,6 +122,9 @@ def load():
     L.vit_hip_tail_biting_workspace_bytes.restype = sz
     L.vit_hip_tail_biting_workspace_bytes.argtypes = [vp, sz, sz, sz, sz]
     L.vit_hip_decode_tail_biting_batch.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, vp, vp, vp, vp]
+    L.vit_hip_stream_workspace_bytes.restype = sz
+    L.vit_hip_stream_workspace_bytes.argtypes = [vp, sz, sz, sz, sz, C.c_uint]
+    L.vit_hip_decode_stream.argtypes = [vp, vp, sz, sz, sz, sz, C.c_uint, vp, sz, vp, C.POINTER(sz), vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -8,6 +8,7 @@
 #include "kernels_lds.hpp"
 #include "kernels_lds2.hpp"
 #include "kernels_tb.hpp"
+#include "kernels_stream.hpp"
 #include "reg_jit.hpp"
 
 using namespace vit;
@@ -431,14 +432,15 @@ int launched(vit_hip_handle h, int rc, const char* what) {
 
 int vit::update_batch_impl(vit_hip_handle h, const void* d_symbols, size_t sym_stride, size_t frames, size_t first_step, size_t n_steps,
                            size_t L, void* d_workspace, size_t workspace_bytes, const void* d_metrics_in, void* d_metrics_out,
-                           uint64_t* d_renorm_sum, const uint32_t* d_start_state, vit_hip_stream_t stream) {
+                           uint64_t* d_renorm_sum, const uint32_t* d_start_state, vit_hip_stream_t stream, bool overlapped_chunks) {
     if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
     if (frames == 0) return VIT_HIP_OK;
     if (!d_symbols || !d_workspace) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace is NULL");
     if (first_step + n_steps > L + (size_t)h->K - 1) return fail(VIT_HIP_ERR_INVALID_ARG, "steps exceed traceback length + K-1");
     if (n_steps > 0x7FFFFFF0u || frames > 0x7FFFFFF0u) return fail(VIT_HIP_ERR_INVALID_ARG, "batch too large");
     if (sym_stride == 0) sym_stride = n_steps * (size_t)h->R;
-    if (sym_stride < n_steps * (size_t)h->R) return fail(VIT_HIP_ERR_INVALID_ARG, "symbol_frame_stride shorter than one chunk");
+    // the windows of one stream overlap (vit_hip_decode_stream: the kernels only read the symbols); every other caller's chunks do not
+    if (sym_stride < n_steps * (size_t)h->R && !overlapped_chunks) return fail(VIT_HIP_ERR_INVALID_ARG, "symbol_frame_stride shorter than one chunk");
     if (workspace_bytes < vit_hip_workspace_bytes(h, frames, L)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
     if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
@@ -676,6 +678,162 @@ int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, si
     w.total = (uint64_t)frames * w.nb;
     w.L = (uint32_t)L; w.head = (uint32_t)head; w.K = (uint32_t)h->K;
     if (vit::tb_launch_window(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting window launch failed");
+    return VIT_HIP_OK;
+}
+
+namespace {
+// the windows of one vit_hip_decode_stream call and its caller-owned workspace, every part 256-byte aligned (include/vit_hip.h)
+struct StreamLayout {
+    size_t a = 0, b = 0, n = 0, n_u = 0;           // emitted range [a, b), windows, of which uniform (n_u == n or n - 1)
+    size_t S_u = 0, L_u = 0, nbe_u = 0;            // a uniform window's steps, chainback bits, bytes
+    size_t S_r = 0, L_r = 0, nbe_r = 0;            // the remainder window's (0 when every window has the same length)
+    size_t dec_u = 0, dec_r = 0, met_u = 0, met_r = 0, end_u = 0, end_r = 0, bytes_u = 0, bytes_r = 0, total = 0;
+};
+
+// argument rule of the stream entry points; fills the window bookkeeping of `o` when the arguments pass
+const char* stream_invalid(vit_hip_handle h, size_t T, size_t W, size_t head, size_t tail, unsigned flags, StreamLayout& o) {
+    const size_t K = (size_t)h->K;
+    const bool begin = flags & VIT_HIP_STREAM_BEGIN, end = flags & VIT_HIP_STREAM_END;
+    if (flags & ~(unsigned)(VIT_HIP_STREAM_BEGIN | VIT_HIP_STREAM_END)) return "unknown stream flags";
+    if (head < K - 1 || tail < K - 1) return "head and tail must be >= K-1";
+    if (W < 8 || W < head || W < tail) return "the window must be >= 8, >= head and >= tail";
+    if (T > 0x7FFFFFF0u || W > 0x10000000u) return "segment too large";
+    if (T < head + tail + (begin ? 0 : 1)) return "the segment must hold head + tail steps (and one more without BEGIN)";
+    o.a = begin ? 0 : head;
+    o.b = end ? T - (K - 1) : T - tail;
+    if (o.b <= o.a) return "the segment emits no bit";
+    // b > a >= 0 and T >= head + tail; b >= head: END: T - (K-1) >= head + tail - (K-1) >= head; else T - tail >= head
+    o.n = (o.b - head) / W;
+    if (o.n < 1) o.n = 1;
+    o.S_u = head + W + tail;
+    const size_t last = T - (o.n - 1) * W;          // steps of the last window
+    o.n_u = last == o.S_u ? o.n : o.n - 1;
+    o.S_r = o.n_u == o.n ? 0 : last;
+    // the register plan addresses a tile's symbols through 32-bit offsets with the sign bit kept free (reg_update): the last of a
+    // tile's (at most 128) overlapped windows ends (tile - 1) * W + S_u steps into it; the remainder window is one frame
+    const size_t step_bytes = (size_t)h->R * (size_t)h->soft_bytes;
+    if ((127 * W + o.S_u) * step_bytes + 65536 >= 0x7FFF0000ull || o.S_r * step_bytes + 65536 >= 0x7FFF0000ull)
+        return "window too large for the launchers' 32-bit symbol offsets";
+    return nullptr;
+}
+
+void stream_layout(vit_hip_handle h, StreamLayout& o) {
+    const size_t K1 = (size_t)h->K - 1, row = (size_t)h->N * (size_t)h->error_bytes;
+    o.L_u = o.S_u - K1;
+    o.nbe_u = (o.L_u + 7) / 8;
+    o.L_r = o.S_r ? o.S_r - K1 : 0;
+    o.nbe_r = (o.L_r + 7) / 8;
+    const size_t r = o.S_r ? 1 : 0;
+    o.dec_u = 0;
+    o.dec_r = o.dec_u + (o.n_u ? align_up(vit_hip_workspace_bytes(h, o.n_u, o.L_u), 256) : 0);
+    o.met_u = o.dec_r + (r ? align_up(vit_hip_workspace_bytes(h, 1, o.L_r), 256) : 0);
+    o.met_r = o.met_u + align_up(o.n_u * row, 256);
+    o.end_u = o.met_r + align_up(r * row, 256);
+    o.end_r = o.end_u + align_up(o.n_u * sizeof(uint32_t), 256);
+    o.bytes_u = o.end_r + align_up(r * sizeof(uint32_t), 256);
+    // 16 bytes of slack behind each: the stitch kernel's loads stay inside the rows, this keeps them off the next part anyway
+    o.bytes_r = o.bytes_u + align_up(o.n_u * o.nbe_u + 16, 256);
+    o.total = o.bytes_r + align_up(r * o.nbe_r + 16, 256);
+}
+}  // namespace
+
+size_t vit_hip_stream_workspace_bytes(vit_hip_handle h, size_t T, size_t W, size_t head, size_t tail, unsigned flags) {
+    StreamLayout lay;
+    if (!h || stream_invalid(h, T, W, head, tail, flags, lay)) return 0;
+    stream_layout(h, lay);
+    return lay.total;
+}
+
+int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
+                          void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, size_t* n_bits_out,
+                          vit_hip_stream_t stream) {
+    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
+    StreamLayout lay;
+    if (const char* why = stream_invalid(h, T, W, head, tail, flags, lay)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
+    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
+    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    stream_layout(h, lay);
+    if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
+    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    VIT_HIP_ON_DEVICE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool begin = flags & VIT_HIP_STREAM_BEGIN, end = flags & VIT_HIP_STREAM_END;
+    const bool rem = lay.S_r != 0;
+    uint8_t* ws = (uint8_t*)d_workspace;
+    void* met_u = ws + lay.met_u;
+    void* met_r = ws + lay.met_r;
+    uint32_t* end_u = (uint32_t*)(ws + lay.end_u);
+    uint32_t* end_r = (uint32_t*)(ws + lay.end_r);
+    const size_t row = (size_t)h->N * (size_t)h->error_bytes, step = (size_t)h->R * (size_t)h->soft_bytes;
+
+    // 1. the start metrics of every window, and end state 0 for the last one under END
+    vit::StreamInitArgs in{};
+    in.met_u = met_u;
+    in.met_r = met_r;
+    in.end_zero = !end ? nullptr : rem ? end_r : end_u + (lay.n_u - 1);
+    in.bytes_u = lay.n_u * row;
+    in.bytes_r = rem ? row : 0;
+    in.chunks_u = (in.bytes_u + 15) / 16;
+    in.total_chunks = in.chunks_u + (in.bytes_r + 15) / 16;
+    in.row_bytes = (uint32_t)row;
+    const uint32_t start = h->cfg_raw[1], non_start = h->cfg_raw[2];
+    in.fill = h->error_bytes == 2 ? (start & 0xFFFFu) * 0x00010001u : (start & 0xFFu) * 0x01010101u;
+    in.non_start = h->error_bytes == 2 ? (non_start & 0xFFFFu) * 0x00010001u : (non_start & 0xFFu) * 0x01010101u;
+    in.begin = begin ? 1u : 0u;
+    if (vit::stream_launch_init(h->error_bytes, in, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream init launch failed");
+
+    // 2. the plan's own update, resumed in place from those metrics: the uniform windows as one batch whose frame stride is W steps
+    //    of the caller's buffer (the windows overlap; nothing is gathered), then the longer last window as a batch of one
+    int rc;
+    if (lay.n_u) {
+        rc = update_batch_impl(h, d_symbols, W * (size_t)h->R, lay.n_u, 0, lay.S_u, lay.L_u, ws + lay.dec_u, lay.dec_r - lay.dec_u, met_u,
+                               met_u, nullptr, nullptr, stream, true);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+    if (rem) {
+        rc = update_batch_impl(h, (const uint8_t*)d_symbols + (lay.n - 1) * W * step, 0, 1, 0, lay.S_r, lay.L_r, ws + lay.dec_r,
+                               lay.met_u - lay.dec_r, met_r, met_r, nullptr, nullptr, stream);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+
+    // 3. end state = smallest final metric, for every window but the last one under END
+    vit::TbSelectArgs s{};
+    s.log2N = (uint32_t)(h->K - 1);
+    s.metrics = met_u;
+    s.end_ws = end_u;
+    s.frames = (uint32_t)(lay.n_u - (end && !rem ? 1 : 0));
+    if (s.frames && vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
+    if (rem && !end) {
+        s.metrics = met_r;
+        s.end_ws = end_r;
+        s.frames = 1;
+        if (vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
+    }
+
+    // 4. the plan's own chainback of every window over all its steps, from those states
+    if (lay.n_u) {
+        rc = chainback_batch_impl(h, ws + lay.dec_u, lay.n_u, lay.L_u, ws + lay.bytes_u, end_u, stream, 0);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+    if (rem) {
+        rc = chainback_batch_impl(h, ws + lay.dec_r, 1, lay.L_r, ws + lay.bytes_r, end_r, stream, 0);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+
+    // 5. each window's share of the output, as one bit stream
+    vit::StreamStitchArgs w{};
+    w.rows_u = ws + lay.bytes_u;
+    w.row_r = ws + lay.bytes_r;
+    w.out = d_bytes_out;
+    w.nb = (lay.b - lay.a + 7) / 8;
+    w.chunks = (w.nb + 15) / 16;
+    w.a = (uint32_t)lay.a; w.b = (uint32_t)lay.b;
+    w.n = (uint32_t)lay.n; w.n_u = (uint32_t)lay.n_u;
+    w.W = (uint32_t)W; w.head = (uint32_t)head;
+    w.nbe_u = (uint32_t)lay.nbe_u; w.nbe_r = (uint32_t)lay.nbe_r;
+    w.out_aligned = ((uintptr_t)d_bytes_out & 15u) == 0 ? 1u : 0u;
+    if (vit::stream_launch_stitch(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream stitch launch failed");
+    if (n_bits_out) *n_bits_out = lay.b - lay.a;
     return VIT_HIP_OK;
 }
 

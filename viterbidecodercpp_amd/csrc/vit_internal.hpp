@@ -1,8 +1,8 @@
 // vit_internal.hpp -- what the translation units of the C ABI share: the decoder handle, the error path, and the few entry points
 // one route calls in another.  Each kernel is launched from exactly ONE unit (there is no -fgpu-rdc: a kernel referenced from two
 // units would be emitted twice):
-//   vit_hip.hip      handle, plans, batched update / chainback / decode / export / depuncture / reset, tail-biting
-//                    (kernels_lds.hpp, kernels_lds2.hpp, kernels_tb.hpp; the register plan through reg_plan.hpp / reg_inst.hip)
+//   vit_hip.hip      handle, plans, batched update / chainback / decode / export / depuncture / reset, tail-biting, one long stream
+//                    (kernels_lds.hpp, kernels_lds2.hpp, kernels_tb.hpp, kernels_stream.hpp; the register plan through reg_plan.hpp / reg_inst.hip)
 //   vit_pipeline.hip vit_hip_pipeline_* and its schedule rules (no kernel of its own)
 //   vit_host.hip     the single-decoder host route and the frame route (kernels_one.hpp)
 //   vit_tools.hip    synth, bit-error count, shader clock, kernel listing, precompile, RCCL table broadcast (kernels_synth.hpp)
@@ -125,7 +125,7 @@ inline void kernel_resources_to_abi(const kd::KernelResources& r, unsigned dyn_l
 // reset + update (d_metrics_in == null, first_step == 0) or resumed update: one body behind both entry points
 int update_batch_impl(vit_hip_handle h, const void* d_symbols, size_t sym_stride, size_t frames, size_t first_step, size_t n_steps,
                       size_t L, void* d_workspace, size_t workspace_bytes, const void* d_metrics_in, void* d_metrics_out,
-                      uint64_t* d_renorm_sum, const uint32_t* d_start_state, vit_hip_stream_t stream);
+                      uint64_t* d_renorm_sum, const uint32_t* d_start_state, vit_hip_stream_t stream, bool overlapped_chunks = false);
 // alt_kernel: the code's other chainback kernel (K = 7: the LDS-ring body, K = 9: the cooperative one); ignored by codes with one
 int chainback_batch_impl(vit_hip_handle h, const void* d_workspace, size_t frames, size_t L, uint8_t* d_bytes_out,
                          const uint32_t* d_end_state, vit_hip_stream_t stream, unsigned wave_priority, bool alt_kernel = false);

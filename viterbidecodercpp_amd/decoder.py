@@ -517,6 +517,55 @@ class BatchDecoder:
             self._stream()))
         return (out, end_state_out, ok_out) if want_extra else out
 
+    def _stream_args(self, window, head, tail, begin, end):
+        head, tail = self._tb_extension(head, tail)
+        window = 1024 if window is None else int(window)
+        return window, head, tail, (_lib.STREAM_BEGIN if begin else 0) | (_lib.STREAM_END if end else 0)
+
+    def stream_workspace_bytes(self, steps: int, begin=True, end=False, window: int = None, head: int = None, tail: int = None) -> int:
+        window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
+        return _lib.load().vit_hip_stream_workspace_bytes(self._handle._h, steps, window, head, tail, flags)
+
+    def decode_stream(self, symbols, begin=True, end=False, window: int = None, head: int = None, tail: int = None, out=None,
+                      workspace=None):
+        """one segment [T][R] of ONE long unterminated stream, decoded as overlapped windows of `window` steps (default 1024) with
+        `head` steps of lead-in and `tail` of look-ahead (default 8*(K-1) each): vit_hip_decode_stream.  begin: step 0 is the
+        encoder's start (else the first `head` steps were emitted by the previous call); end: the last K-1 steps are the zero
+        tail (else the last `tail` steps are look-ahead only: the next segment starts head + tail steps before this one's end).
+        returns (bytes [ceil(n_bits/8)] uint8 on the device, MSB-first, pad bits 0; n_bits).  Segments of head + n*window + tail
+        steps run as one uniform batch."""
+        t = self.torch
+        window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
+        want = t.int16 if self.soft_bytes == 2 else t.int8
+        if symbols.dtype != want or not symbols.is_cuda or not symbols.is_contiguous() or symbols.numel() % self.R != 0:
+            raise ValueError(f"symbols must be a contiguous {want} CUDA tensor of [steps][R]")
+        T = symbols.numel() // self.R
+        need = _lib.load().vit_hip_stream_workspace_bytes(self._handle._h, T, window, head, tail, flags)
+        if need == 0:
+            raise ValueError(f"stream decoding needs head, tail >= K-1, window >= 8, head, tail, and a segment that emits bits "
+                             f"(K = {self.K}, steps = {T}, window = {window}, head = {head}, tail = {tail})")
+        if workspace is not None:
+            if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
+                raise ValueError("workspace too small or not 256-byte aligned")
+            ws = workspace
+        else:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
+            ws = self._ws
+        a = 0 if begin else head
+        b = T - (self.K - 1) if end else T - tail
+        nb = (b - a + 7) // 8
+        if out is None:
+            out = t.empty(nb, dtype=t.uint8, device=self.device)
+        elif out.dtype != t.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != nb:
+            raise ValueError(f"out must be a contiguous uint8 CUDA tensor of {nb} elements")
+        n_bits = C.c_size_t(0)
+        _lib.check(_lib.load().vit_hip_decode_stream(
+            self._handle._h, C.c_void_p(symbols.data_ptr()), T, window, head, tail, flags, C.c_void_p(ws.data_ptr()),
+            ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()), C.byref(n_bits), self._stream()))
+        return out, int(n_bits.value)
+
     def depuncture(self, punctured, mask, out=None):
         """Depuncturing front-end (examples/helpers/puncture_code_helpers.h:17-55) for a batch: `punctured` is the device
         tensor [F][P] of transmitted symbols, `mask` the puncturing vector over one whole frame (truthy = transmitted, one
@@ -592,6 +641,76 @@ class BatchDecoder:
         _lib.check(_lib.load().vit_hip_export_decisions(self._handle._h, C.c_void_p(ws.data_ptr()), frames, n_steps, L,
                                                         C.c_void_p(dec.data_ptr()), self._stream()))
         return dec
+
+
+class StreamDecoder:
+    """A chunked receiver on top of BatchDecoder.decode_stream: push() symbols of one long stream as they arrive, get decoded
+    bytes back; finish() ends the stream (its last K-1 steps are the zero tail).
+
+    Every internal call is a segment of head + n*window + tail steps on the window grid (one uniform batch), BEGIN on the first.
+    What does not fill a window yet stays on the device: the last head + tail steps of the segment just decoded (the next one's
+    lead-in and this one's look-ahead) and at least one more window (window + K-1 steps), so that the final segment under END
+    always holds a full window -- with that, pushes of ANY sizes plus finish() decode to exactly the bits of ONE decode_stream
+    call over the whole stream (tests/test_stream_cpu.py: chunked vs one call).  Whole bytes only: the sub-byte remainder is
+    carried to the next call; finish() pads the last byte with zeros.  `n_bits` counts the bits returned so far."""
+
+    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None):
+        self.decoder = decoder
+        self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
+        if decoder.stream_workspace_bytes(self.head + self.window + self.tail, True, False, self.window, self.head, self.tail) == 0:
+            raise ValueError("window, head, tail outside the argument rule of vit_hip_decode_stream")
+        self.n_bits = 0
+        self.calls = []                       # (steps, begin, end) of every internal call, for inspection
+        self._first = True
+        self._done = False
+        self._pending = None                  # device tensor [steps][R]
+        self._carry = np.zeros(0, dtype=np.uint8)
+
+    def _append(self, symbols):
+        if symbols is None:
+            return
+        t = self.decoder.torch
+        want = t.int16 if self.decoder.soft_bytes == 2 else t.int8
+        if symbols.dtype != want or not symbols.is_cuda or symbols.numel() % self.decoder.R != 0:
+            raise ValueError(f"symbols must be a {want} CUDA tensor of [steps][R]")
+        symbols = symbols.reshape(-1, self.decoder.R)
+        self._pending = symbols.contiguous() if self._pending is None else t.cat([self._pending, symbols])
+
+    def _emit(self, out, n_bits, final):
+        bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy())[:n_bits]])
+        keep = bits.size if final else bits.size - bits.size % 8
+        self._carry = bits[keep:]
+        self.n_bits += keep
+        return np.packbits(bits[:keep], bitorder="big").tobytes()
+
+    def push(self, symbols) -> bytes:
+        if self._done:
+            raise RuntimeError("the stream is finished")
+        self._append(symbols)
+        P = 0 if self._pending is None else self._pending.shape[0]
+        hold = self.head + self.window + self.decoder.K - 1
+        if P < hold + self.window:
+            return b""
+        n = (P - hold) // self.window
+        T = self.head + n * self.window + self.tail
+        out, n_bits = self.decoder.decode_stream(self._pending[:T], self._first, False, self.window, self.head, self.tail)
+        self.calls.append((T, self._first, False))
+        data = self._emit(out, n_bits, False)
+        self._pending = self._pending[n * self.window:].contiguous()
+        self._first = False
+        return data
+
+    def finish(self, symbols=None) -> bytes:
+        if self._done:
+            raise RuntimeError("the stream is finished")
+        self._append(symbols)
+        if self._pending is None:
+            raise ValueError("an empty stream")
+        out, n_bits = self.decoder.decode_stream(self._pending, self._first, True, self.window, self.head, self.tail)
+        self.calls.append((self._pending.shape[0], self._first, True))
+        self._done = True
+        self._pending = None
+        return self._emit(out, n_bits, True)
 
 
 class DecodePipeline:
