@@ -34,6 +34,8 @@
  *   vit_hip_decode_stream     one long unterminated stream as overlapped windows: no reference counterpart either (the reference
  *                             decodes one terminated frame per Core); written in terms of its reset / update / chainback (rule
  *                             below), with vit_hip_stream_workspace_bytes
+ *   vit_hip_decode_streams    several such streams in lockstep on one shared window grid, with the launches of one
+ *                             vit_hip_decode_stream call (rule below), with vit_hip_streams_workspace_bytes
  *   vit_hip_broadcast_table   "Branch table can be shared between multiple decoders"   README.md:14,
  *                             viterbi_branch_table.h:17-18, one decoder per worker examples/run_benchmark.cpp:193-197:
  *                             here the workers are GPUs and the table travels once over RCCL/xGMI
@@ -401,7 +403,7 @@ int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, si
  * metrics, update, end-state select, chainback, stitch), up to EIGHT otherwise (a second update, select and chainback for the
  * longer last window; no select for a window that ends in state 0) -- with no allocation and no synchronisation, and can be
  * captured into a hipGraph; several may be in flight on one handle, each with its own workspace.  ONE stream per call: a caller
- * with several streams issues several calls (the update kernels take one frame stride; a second level would mean changing them).
+ * with several streams that advance in lockstep hands them all to vit_hip_decode_streams (below) in one call.
  * Punctured streams need nothing new: vit_hip_depuncture_batch with `frames` = the number of puncturing periods turns the received
  * stream into the contiguous [T][R] buffer this call reads.
  * vit_hip_stream_workspace_bytes returns 0 for arguments the decode call rejects. */
@@ -411,6 +413,40 @@ size_t vit_hip_stream_workspace_bytes(vit_hip_handle h, size_t T, size_t W, size
 int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
                           void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, size_t* n_bits_out,
                           vit_hip_stream_t stream);
+
+/* ---- many lockstep streams in one call, on one shared window grid -----------------------------------------------------------
+ * A receiver pushes a few milliseconds at a time -- tens to hundreds of windows -- for several streams at once (the sub-channels
+ * of a DAB ensemble, the carriers of a multi-carrier downlink, the virtual channels of a CCSDS link).  One call decodes one
+ * segment of EVERY stream with the launches of one vit_hip_decode_stream call.
+ *   d_symbols    [n_streams][pitch][R] soft_t: stream s occupies steps [s pitch, s pitch + T); what lies between T and pitch is
+ *                padding whose content the result does not depend on (it is read).  The last stream needs only T steps: the
+ *                buffer holds (n_streams - 1) pitch + T steps.
+ *   d_bytes_out  [n_streams][out_pitch_bytes]
+ * Rule, bit-exact: row s of d_bytes_out holds exactly the bytes vit_hip_decode_stream returns for stream s's T steps with the same
+ * W, head, tail and flags -- ceil(n_out/8) bytes, pad bits 0; the bytes of a row behind them are not written.  *n_bits_out = n_out
+ * as there.  The window bookkeeping of each stream (a, b, n, the longer last window, BEGIN, END) is that of
+ * vit_hip_decode_stream, unchanged.  All streams share T, W, head, tail and flags: they run in lockstep.  Per-stream lengths or
+ * flags are out of scope (a caller with such streams groups them by shape, or calls vit_hip_decode_stream per stream).
+ * How: pitch = m W, so the windows of all streams lie on ONE grid of stride W in the caller's buffer, and the plan's resumed update
+ * takes them as one batch of frame stride W R exactly as for one stream.  Between the last uniform window of stream s and the
+ * first window of stream s+1 lie m - n_u grid windows that straddle the two segments: these BRIDGE windows are decoded like any
+ * other (they read only bytes inside the buffer) and their output is dropped; the last stream's are not launched.  Launched grid
+ * windows: (n_streams - 1) m + n_u for n_streams n_u useful ones; with T = head + n W + tail the smallest m is n + 1 (n + 2 when
+ * head + tail > W): an overhead of 1/n to 2/n.  The longer last windows of all streams are a second batch of n_streams frames at
+ * stride pitch.  When a stream is one window of its own length (n_u = 0) that batch is all there is and the grid is not launched.
+ * Arguments: everything vit_hip_decode_stream demands, and n_streams >= 1, pitch >= T, pitch % W == 0, out_pitch_bytes >=
+ * ceil(n_out/8); (n_streams - 1) m + n_u and n_streams < 2^31 - 16; with a longer last window and n_streams > 1 on the register
+ * plan, pitch * R * sizeof(soft_t) * workspace_tile_frames < 2^31 - 2^17 (the launchers' 32-bit counters).  Everything else is
+ * VIT_HIP_ERR_INVALID_ARG and nothing is launched.  Workspace as for one stream (VIT_HIP_ERR_WORKSPACE), sized by
+ * vit_hip_streams_workspace_bytes, which returns 0 for arguments the decode call rejects.
+ * Launches: the counts of ONE stream whatever n_streams is -- FIVE when every window has one length, at most EIGHT otherwise.  The
+ * call only enqueues on `stream`, allocates nothing, synchronises nothing and can be captured into a hipGraph; several may be in
+ * flight on one handle, each with its own workspace. */
+size_t vit_hip_streams_workspace_bytes(vit_hip_handle h, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head, size_t tail,
+                                       unsigned flags);
+int vit_hip_decode_streams(vit_hip_handle h, const void* d_symbols, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head,
+                           size_t tail, unsigned flags, void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out,
+                           size_t out_pitch_bytes, size_t* n_bits_out, vit_hip_stream_t stream);
 
 /* ---- multi-GPU set-up for C/C++ hosts ----------------------------------------------------------------------------------- */
 

@@ -99,6 +99,24 @@ public:
               "vit_hip_decode_stream");
         return n_bits;
     }
+    // n_streams lockstep streams in one call on one shared window grid (vit_hip_decode_streams): d_symbols [n_streams][pitch][R],
+    // stream s in steps [s*pitch, s*pitch + steps), pitch a multiple of the window; row s of d_bytes_out [n_streams][out_pitch_bytes]
+    // is what decode_stream returns for stream s.  Defaults as decode_stream.  Returns the number of bits written to each row.
+    size_t streams_workspace_bytes(size_t n_streams, size_t pitch, size_t steps, bool begin, bool end, size_t window = 0,
+                                   size_t head = 0, size_t tail = 0) const {
+        return vit_hip_streams_workspace_bytes(m_hip, n_streams, pitch, steps, window ? window : 1024, extension(head), extension(tail),
+                                               stream_flags(begin, end));
+    }
+    size_t decode_streams(const soft_t* d_symbols, size_t n_streams, size_t pitch, size_t steps, bool begin, bool end, void* d_workspace,
+                          size_t workspace_size, uint8_t* d_bytes_out, size_t out_pitch_bytes, size_t window = 0, size_t head = 0,
+                          size_t tail = 0, void* stream = nullptr) {
+        size_t n_bits = 0;
+        check(vit_hip_decode_streams(m_hip, d_symbols, n_streams, pitch, steps, window ? window : 1024, extension(head), extension(tail),
+                                     stream_flags(begin, end), d_workspace, workspace_size, d_bytes_out, out_pitch_bytes, &n_bits,
+                                     stream),
+              "vit_hip_decode_streams");
+        return n_bits;
+    }
     // test / measurement harness on the device: the BER harness's frame generator (examples/run_snr_ber.cpp:311-359) and
     // get_total_bit_errors (examples/helpers/test_helpers.h:95-104)
     void synth(size_t frames, size_t total_bits, uint64_t seed, uint64_t first_frame, float ebn0_db, bool noise_free,

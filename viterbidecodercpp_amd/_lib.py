@@ -31,6 +31,7 @@ EXPORTS = [
     "vit_hip_precompile", "vit_hip_update_host_lazy", "vit_hip_chainback_host_lazy", "vit_hip_fetch_decisions_host",
     "vit_hip_tail_biting_workspace_bytes", "vit_hip_decode_tail_biting_batch",
     "vit_hip_stream_workspace_bytes", "vit_hip_decode_stream",
+    "vit_hip_streams_workspace_bytes", "vit_hip_decode_streams",
 ]
 
 
@@ -125,6 +126,9 @@ def load():
     L.vit_hip_stream_workspace_bytes.restype = sz
     L.vit_hip_stream_workspace_bytes.argtypes = [vp, sz, sz, sz, sz, C.c_uint]
     L.vit_hip_decode_stream.argtypes = [vp, vp, sz, sz, sz, sz, C.c_uint, vp, sz, vp, C.POINTER(sz), vp]
+    L.vit_hip_streams_workspace_bytes.restype = sz
+    L.vit_hip_streams_workspace_bytes.argtypes = [vp, sz, sz, sz, sz, sz, sz, C.c_uint]
+    L.vit_hip_decode_streams.argtypes = [vp, vp, sz, sz, sz, sz, sz, sz, C.c_uint, vp, sz, vp, sz, C.POINTER(sz), vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

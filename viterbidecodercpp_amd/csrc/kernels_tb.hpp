@@ -89,7 +89,12 @@ struct TbSelectArgs {
     uint32_t* end_ws;        // [F]: the end states chainback reads
     uint32_t* end_out;       // [F] or null: the caller's copy
     uint32_t frames, log2N;
+    uint32_t keep_period;    // 0: every frame is written.  Else the frames f with f % keep_period == keep_phase keep the end state
+    uint32_t keep_phase;     // the caller put there (vit_hip_decode_streams: the last window of every stream ends in state 0)
 };
+
+// such a frame's end state stays as it is
+__device__ inline bool tb_select_keeps(const TbSelectArgs& a, uint32_t f) { return a.keep_period && f % a.keep_period == a.keep_phase; }
 
 // the packed key (metric << log2 N) | state of VB / sizeof(error_t) consecutive states, reduced to the lane's minimum: the minimum
 // key is the smallest metric (unsigned) and, among equal metrics, the lowest state.  log2 N <= 15 and error_t <= 16 bits: 31 bits.
@@ -137,7 +142,7 @@ __global__ void __launch_bounds__(256) tb_select_small_kernel(TbSelectArgs a) {
         const uint32_t o = __shfl_xor(key, (int)off);
         key = o < key ? o : key;
     }
-    if (f < a.frames && p == 0) {
+    if (f < a.frames && p == 0 && !tb_select_keeps(a, f)) {
         const uint32_t s = key & (N - 1u);
         a.end_ws[f] = s;
         if (a.end_out) a.end_out[f] = s;
@@ -165,7 +170,7 @@ __global__ void __launch_bounds__(256) tb_select_large_kernel(TbSelectArgs a) {
     }
     if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = key;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && !tb_select_keeps(a, f)) {
         for (uint32_t w = 1; w < blockDim.x / 64; ++w) key = part[w] < key ? part[w] : key;
         const uint32_t s = key & (N - 1u);
         a.end_ws[f] = s;

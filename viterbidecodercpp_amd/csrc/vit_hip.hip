@@ -682,11 +682,14 @@ int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, si
 }
 
 namespace {
-// the windows of one vit_hip_decode_stream call and its caller-owned workspace, every part 256-byte aligned (include/vit_hip.h)
+// the windows of one vit_hip_decode_stream / vit_hip_decode_streams call and its caller-owned workspace, every part 256-byte aligned
+// (include/vit_hip.h).  One stream is n_streams = 1: rows_u = n_u and one remainder frame, what vit_hip_decode_stream always laid out.
 struct StreamLayout {
-    size_t a = 0, b = 0, n = 0, n_u = 0;           // emitted range [a, b), windows, of which uniform (n_u == n or n - 1)
+    size_t a = 0, b = 0, n = 0, n_u = 0;           // per stream: emitted range [a, b), windows, of which uniform (n_u == n or n - 1)
     size_t S_u = 0, L_u = 0, nbe_u = 0;            // a uniform window's steps, chainback bits, bytes
     size_t S_r = 0, L_r = 0, nbe_r = 0;            // the remainder window's (0 when every window has the same length)
+    size_t n_streams = 1, period = 0;              // streams; grid windows from one stream's window 0 to the next one's (pitch / W)
+    size_t rows_u = 0, rows_r = 0;                 // launched grid windows (n_streams - 1) * period + n_u; remainder frames
     size_t dec_u = 0, dec_r = 0, met_u = 0, met_r = 0, end_u = 0, end_r = 0, bytes_u = 0, bytes_r = 0, total = 0;
 };
 
@@ -714,6 +717,29 @@ const char* stream_invalid(vit_hip_handle h, size_t T, size_t W, size_t head, si
     const size_t step_bytes = (size_t)h->R * (size_t)h->soft_bytes;
     if ((127 * W + o.S_u) * step_bytes + 65536 >= 0x7FFF0000ull || o.S_r * step_bytes + 65536 >= 0x7FFF0000ull)
         return "window too large for the launchers' 32-bit symbol offsets";
+    o.n_streams = 1;
+    o.period = 0;
+    o.rows_u = o.n_u;
+    o.rows_r = o.S_r ? 1 : 0;
+    return nullptr;
+}
+
+// the same for n_streams lockstep streams `pitch` steps apart: each stream under the rule above, all of them on one grid of W steps
+const char* streams_invalid(vit_hip_handle h, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
+                            StreamLayout& o) {
+    if (const char* why = stream_invalid(h, T, W, head, tail, flags, o)) return why;
+    if (n_streams < 1 || n_streams > 0x7FFFFFF0u) return "n_streams must be >= 1 (and within the launchers' batch limit)";
+    if (pitch < T || pitch % W != 0) return "pitch must be >= T and a multiple of the window";
+    o.n_streams = n_streams;
+    o.period = pitch / W;                           // > n_u, >= n: the last window of a stream ends inside its pitch
+    // no useful window on the grid (every stream is one remainder window): the grid is not launched
+    o.rows_u = o.n_u ? (n_streams - 1) * o.period + o.n_u : 0;
+    o.rows_r = o.S_r ? n_streams : 0;
+    if (o.rows_u > 0x7FFFFFF0u) return "too many windows for one batch";
+    // the remainder windows are a batch at stride pitch: a register-plan tile of them spans tile * pitch steps (reg_update's bound)
+    const size_t tile = h->plan == VIT_HIP_PLAN_REG ? (size_t)h->reg_code.tile : 1;
+    if (o.rows_r > 1 && pitch * (size_t)h->R * (size_t)h->soft_bytes * tile + 65536 >= 0x7FFF0000ull)
+        return "pitch too large for the launchers' 32-bit symbol offsets";
     return nullptr;
 }
 
@@ -723,17 +749,116 @@ void stream_layout(vit_hip_handle h, StreamLayout& o) {
     o.nbe_u = (o.L_u + 7) / 8;
     o.L_r = o.S_r ? o.S_r - K1 : 0;
     o.nbe_r = (o.L_r + 7) / 8;
-    const size_t r = o.S_r ? 1 : 0;
     o.dec_u = 0;
-    o.dec_r = o.dec_u + (o.n_u ? align_up(vit_hip_workspace_bytes(h, o.n_u, o.L_u), 256) : 0);
-    o.met_u = o.dec_r + (r ? align_up(vit_hip_workspace_bytes(h, 1, o.L_r), 256) : 0);
-    o.met_r = o.met_u + align_up(o.n_u * row, 256);
-    o.end_u = o.met_r + align_up(r * row, 256);
-    o.end_r = o.end_u + align_up(o.n_u * sizeof(uint32_t), 256);
-    o.bytes_u = o.end_r + align_up(r * sizeof(uint32_t), 256);
+    o.dec_r = o.dec_u + (o.rows_u ? align_up(vit_hip_workspace_bytes(h, o.rows_u, o.L_u), 256) : 0);
+    o.met_u = o.dec_r + (o.rows_r ? align_up(vit_hip_workspace_bytes(h, o.rows_r, o.L_r), 256) : 0);
+    o.met_r = o.met_u + align_up(o.rows_u * row, 256);
+    o.end_u = o.met_r + align_up(o.rows_r * row, 256);
+    o.end_r = o.end_u + align_up(o.rows_u * sizeof(uint32_t), 256);
+    o.bytes_u = o.end_r + align_up(o.rows_r * sizeof(uint32_t), 256);
     // 16 bytes of slack behind each: the stitch kernel's loads stay inside the rows, this keeps them off the next part anyway
-    o.bytes_r = o.bytes_u + align_up(o.n_u * o.nbe_u + 16, 256);
-    o.total = o.bytes_r + align_up(r * o.nbe_r + 16, 256);
+    o.bytes_r = o.bytes_u + align_up(o.rows_u * o.nbe_u + 16, 256);
+    o.total = o.bytes_r + align_up(o.rows_r * o.nbe_r + 16, 256);
+}
+
+// the launches of both entry points, once the arguments have passed.  pitch and out_pitch: unused with one stream
+int decode_streams_launch(vit_hip_handle h, const StreamLayout& lay, const void* d_symbols, size_t pitch, size_t W, size_t head,
+                          unsigned flags, void* d_workspace, uint8_t* d_bytes_out, size_t out_pitch, vit_hip_stream_t stream) {
+    VIT_HIP_ON_DEVICE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool begin = flags & VIT_HIP_STREAM_BEGIN, end = flags & VIT_HIP_STREAM_END;
+    const bool rem = lay.S_r != 0, many = lay.n_streams > 1;
+    uint8_t* ws = (uint8_t*)d_workspace;
+    void* met_u = ws + lay.met_u;
+    void* met_r = ws + lay.met_r;
+    uint32_t* end_u = (uint32_t*)(ws + lay.end_u);
+    uint32_t* end_r = (uint32_t*)(ws + lay.end_r);
+    const size_t row = (size_t)h->N * (size_t)h->error_bytes, step = (size_t)h->R * (size_t)h->soft_bytes;
+
+    // 1. the start metrics of every window, and end state 0 for the last one of every stream under END
+    vit::StreamInitArgs in{};
+    in.met_u = met_u;
+    in.met_r = met_r;
+    if (end) {
+        in.end_zero = rem ? end_r : end_u + (lay.n_u - 1);
+        in.end_zero_count = (uint32_t)lay.n_streams;
+        in.end_zero_stride = (uint32_t)(rem ? 1 : lay.period);
+    }
+    in.bytes_u = lay.rows_u * row;
+    in.bytes_r = lay.rows_r * row;
+    in.chunks_u = (in.bytes_u + 15) / 16;
+    in.total_chunks = in.chunks_u + (in.bytes_r + 15) / 16;
+    in.row_bytes = (uint32_t)row;
+    in.row_shift = (uint32_t)(h->K - 1) + (h->error_bytes == 2 ? 1u : 0u);
+    const uint32_t start = h->cfg_raw[1], non_start = h->cfg_raw[2];
+    in.fill = h->error_bytes == 2 ? (start & 0xFFFFu) * 0x00010001u : (start & 0xFFu) * 0x01010101u;
+    in.non_start = h->error_bytes == 2 ? (non_start & 0xFFFFu) * 0x00010001u : (non_start & 0xFFu) * 0x01010101u;
+    // window 0 of a stream is row s * period of the grid; with one stream row 0 alone (a period no other row reaches)
+    in.begin_period_u = !begin || !lay.rows_u ? 0u : (uint32_t)(many ? lay.period : lay.rows_u);
+    in.begin_r = begin && !lay.n_u ? 1u : 0u;
+    if (vit::stream_launch_init(h->error_bytes, in, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream init launch failed");
+
+    // 2. the plan's own update, resumed in place from those metrics: the grid windows as one batch whose frame stride is W steps of
+    //    the caller's buffer (the windows overlap; nothing is gathered), then the longer last windows as a batch of one frame per
+    //    stream at stride pitch
+    int rc;
+    if (lay.rows_u) {
+        rc = update_batch_impl(h, d_symbols, W * (size_t)h->R, lay.rows_u, 0, lay.S_u, lay.L_u, ws + lay.dec_u, lay.dec_r - lay.dec_u, met_u,
+                               met_u, nullptr, nullptr, stream, true);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+    if (rem) {
+        rc = update_batch_impl(h, (const uint8_t*)d_symbols + (lay.n - 1) * W * step, many ? pitch * (size_t)h->R : 0, lay.rows_r, 0, lay.S_r,
+                               lay.L_r, ws + lay.dec_r, lay.met_u - lay.dec_r, met_r, met_r, nullptr, nullptr, stream);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+
+    // 3. end state = smallest final metric, for every window but the last one of a stream under END
+    vit::TbSelectArgs s{};
+    s.log2N = (uint32_t)(h->K - 1);
+    s.metrics = met_u;
+    s.end_ws = end_u;
+    s.frames = (uint32_t)(lay.rows_u - (end && !rem && lay.rows_u ? 1 : 0));
+    if (end && !rem && many) {
+        s.keep_period = (uint32_t)lay.period;
+        s.keep_phase = (uint32_t)(lay.n_u - 1);
+    }
+    if (s.frames && vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
+    if (rem && !end) {
+        s.metrics = met_r;
+        s.end_ws = end_r;
+        s.frames = (uint32_t)lay.rows_r;
+        s.keep_period = 0;
+        if (vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
+    }
+
+    // 4. the plan's own chainback of every window over all its steps, from those states
+    if (lay.rows_u) {
+        rc = chainback_batch_impl(h, ws + lay.dec_u, lay.rows_u, lay.L_u, ws + lay.bytes_u, end_u, stream, 0);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+    if (rem) {
+        rc = chainback_batch_impl(h, ws + lay.dec_r, lay.rows_r, lay.L_r, ws + lay.bytes_r, end_r, stream, 0);
+        if (rc != VIT_HIP_OK) return rc;
+    }
+
+    // 5. each window's share of the output, as one bit stream per stream; the bridge windows' rows are not read
+    vit::StreamStitchArgs w{};
+    w.rows_u = ws + lay.bytes_u;
+    w.row_r = ws + lay.bytes_r;
+    w.out = d_bytes_out;
+    w.out_pitch = many ? out_pitch : 0;
+    w.n_streams = (uint32_t)lay.n_streams;
+    w.period = (uint32_t)lay.period;
+    w.nb = (lay.b - lay.a + 7) / 8;
+    w.chunks = (w.nb + 15) / 16;
+    w.a = (uint32_t)lay.a; w.b = (uint32_t)lay.b;
+    w.n = (uint32_t)lay.n; w.n_u = (uint32_t)lay.n_u;
+    w.W = (uint32_t)W; w.head = (uint32_t)head;
+    w.nbe_u = (uint32_t)lay.nbe_u; w.nbe_r = (uint32_t)lay.nbe_r;
+    w.out_aligned = ((uintptr_t)d_bytes_out & 15u) == 0 && (w.out_pitch & 15u) == 0 ? 1u : 0u;
+    if (vit::stream_launch_stitch(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream stitch launch failed");
+    return VIT_HIP_OK;
 }
 }  // namespace
 
@@ -755,84 +880,34 @@ int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, siz
     stream_layout(h, lay);
     if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
     if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    VIT_HIP_ON_DEVICE(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const bool begin = flags & VIT_HIP_STREAM_BEGIN, end = flags & VIT_HIP_STREAM_END;
-    const bool rem = lay.S_r != 0;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    void* met_u = ws + lay.met_u;
-    void* met_r = ws + lay.met_r;
-    uint32_t* end_u = (uint32_t*)(ws + lay.end_u);
-    uint32_t* end_r = (uint32_t*)(ws + lay.end_r);
-    const size_t row = (size_t)h->N * (size_t)h->error_bytes, step = (size_t)h->R * (size_t)h->soft_bytes;
+    const int rc = decode_streams_launch(h, lay, d_symbols, 0, W, head, flags, d_workspace, d_bytes_out, 0, stream);
+    if (rc != VIT_HIP_OK) return rc;
+    if (n_bits_out) *n_bits_out = lay.b - lay.a;
+    return VIT_HIP_OK;
+}
 
-    // 1. the start metrics of every window, and end state 0 for the last one under END
-    vit::StreamInitArgs in{};
-    in.met_u = met_u;
-    in.met_r = met_r;
-    in.end_zero = !end ? nullptr : rem ? end_r : end_u + (lay.n_u - 1);
-    in.bytes_u = lay.n_u * row;
-    in.bytes_r = rem ? row : 0;
-    in.chunks_u = (in.bytes_u + 15) / 16;
-    in.total_chunks = in.chunks_u + (in.bytes_r + 15) / 16;
-    in.row_bytes = (uint32_t)row;
-    const uint32_t start = h->cfg_raw[1], non_start = h->cfg_raw[2];
-    in.fill = h->error_bytes == 2 ? (start & 0xFFFFu) * 0x00010001u : (start & 0xFFu) * 0x01010101u;
-    in.non_start = h->error_bytes == 2 ? (non_start & 0xFFFFu) * 0x00010001u : (non_start & 0xFFu) * 0x01010101u;
-    in.begin = begin ? 1u : 0u;
-    if (vit::stream_launch_init(h->error_bytes, in, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream init launch failed");
+size_t vit_hip_streams_workspace_bytes(vit_hip_handle h, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head, size_t tail,
+                                       unsigned flags) {
+    StreamLayout lay;
+    if (!h || streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay)) return 0;
+    stream_layout(h, lay);
+    return lay.total;
+}
 
-    // 2. the plan's own update, resumed in place from those metrics: the uniform windows as one batch whose frame stride is W steps
-    //    of the caller's buffer (the windows overlap; nothing is gathered), then the longer last window as a batch of one
-    int rc;
-    if (lay.n_u) {
-        rc = update_batch_impl(h, d_symbols, W * (size_t)h->R, lay.n_u, 0, lay.S_u, lay.L_u, ws + lay.dec_u, lay.dec_r - lay.dec_u, met_u,
-                               met_u, nullptr, nullptr, stream, true);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-    if (rem) {
-        rc = update_batch_impl(h, (const uint8_t*)d_symbols + (lay.n - 1) * W * step, 0, 1, 0, lay.S_r, lay.L_r, ws + lay.dec_r,
-                               lay.met_u - lay.dec_r, met_r, met_r, nullptr, nullptr, stream);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-
-    // 3. end state = smallest final metric, for every window but the last one under END
-    vit::TbSelectArgs s{};
-    s.log2N = (uint32_t)(h->K - 1);
-    s.metrics = met_u;
-    s.end_ws = end_u;
-    s.frames = (uint32_t)(lay.n_u - (end && !rem ? 1 : 0));
-    if (s.frames && vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
-    if (rem && !end) {
-        s.metrics = met_r;
-        s.end_ws = end_r;
-        s.frames = 1;
-        if (vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
-    }
-
-    // 4. the plan's own chainback of every window over all its steps, from those states
-    if (lay.n_u) {
-        rc = chainback_batch_impl(h, ws + lay.dec_u, lay.n_u, lay.L_u, ws + lay.bytes_u, end_u, stream, 0);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-    if (rem) {
-        rc = chainback_batch_impl(h, ws + lay.dec_r, 1, lay.L_r, ws + lay.bytes_r, end_r, stream, 0);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-
-    // 5. each window's share of the output, as one bit stream
-    vit::StreamStitchArgs w{};
-    w.rows_u = ws + lay.bytes_u;
-    w.row_r = ws + lay.bytes_r;
-    w.out = d_bytes_out;
-    w.nb = (lay.b - lay.a + 7) / 8;
-    w.chunks = (w.nb + 15) / 16;
-    w.a = (uint32_t)lay.a; w.b = (uint32_t)lay.b;
-    w.n = (uint32_t)lay.n; w.n_u = (uint32_t)lay.n_u;
-    w.W = (uint32_t)W; w.head = (uint32_t)head;
-    w.nbe_u = (uint32_t)lay.nbe_u; w.nbe_r = (uint32_t)lay.nbe_r;
-    w.out_aligned = ((uintptr_t)d_bytes_out & 15u) == 0 ? 1u : 0u;
-    if (vit::stream_launch_stitch(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream stitch launch failed");
+int vit_hip_decode_streams(vit_hip_handle h, const void* d_symbols, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head,
+                           size_t tail, unsigned flags, void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out,
+                           size_t out_pitch_bytes, size_t* n_bits_out, vit_hip_stream_t stream) {
+    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
+    StreamLayout lay;
+    if (const char* why = streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
+    if (out_pitch_bytes < (lay.b - lay.a + 7) / 8) return fail(VIT_HIP_ERR_INVALID_ARG, "out_pitch_bytes shorter than ceil(n_out/8)");
+    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
+    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    stream_layout(h, lay);
+    if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
+    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    const int rc = decode_streams_launch(h, lay, d_symbols, pitch, W, head, flags, d_workspace, d_bytes_out, out_pitch_bytes, stream);
+    if (rc != VIT_HIP_OK) return rc;
     if (n_bits_out) *n_bits_out = lay.b - lay.a;
     return VIT_HIP_OK;
 }

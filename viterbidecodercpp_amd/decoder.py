@@ -566,6 +566,55 @@ class BatchDecoder:
             ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()), C.byref(n_bits), self._stream()))
         return out, int(n_bits.value)
 
+    def streams_workspace_bytes(self, n_streams: int, pitch: int, steps: int, begin=True, end=False, window: int = None,
+                                head: int = None, tail: int = None) -> int:
+        window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
+        return _lib.load().vit_hip_streams_workspace_bytes(self._handle._h, n_streams, pitch, steps, window, head, tail, flags)
+
+    def decode_streams(self, symbols, steps: int = None, begin=True, end=False, window: int = None, head: int = None, tail: int = None,
+                       out=None, workspace=None):
+        """one segment of `steps` trellis steps of EACH of n_streams lockstep streams in one call: vit_hip_decode_streams.  symbols
+        [n_streams][pitch][R], stream s in its first `steps` steps (default: all `pitch` of them), pitch a multiple of `window`; what
+        lies behind `steps` is padding the result does not depend on.  begin / end / window / head / tail as decode_stream, shared
+        by all streams.  returns (bytes [n_streams][ceil(n_bits/8)] uint8 on the device, n_bits): row s is what decode_stream returns
+        for stream s.  `out`: a uint8 CUDA tensor [n_streams][>= ceil(n_bits/8)] with contiguous rows; the bytes of a row behind
+        ceil(n_bits/8) are left as they are and the view of the written part is returned."""
+        t = self.torch
+        window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
+        want = t.int16 if self.soft_bytes == 2 else t.int8
+        if symbols.dtype != want or not symbols.is_cuda or not symbols.is_contiguous() or symbols.dim() != 3 or symbols.shape[2] != self.R:
+            raise ValueError(f"symbols must be a contiguous {want} CUDA tensor of [n_streams][pitch][R]")
+        n_streams, pitch = int(symbols.shape[0]), int(symbols.shape[1])
+        T = pitch if steps is None else int(steps)
+        need = _lib.load().vit_hip_streams_workspace_bytes(self._handle._h, n_streams, pitch, T, window, head, tail, flags)
+        if need == 0:
+            raise ValueError(f"decoding lockstep streams needs what decode_stream needs, n_streams >= 1, pitch >= steps and pitch a "
+                             f"multiple of the window (K = {self.K}, n_streams = {n_streams}, pitch = {pitch}, steps = {T}, "
+                             f"window = {window}, head = {head}, tail = {tail})")
+        if workspace is not None:
+            if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
+                raise ValueError("workspace too small or not 256-byte aligned")
+            ws = workspace
+        else:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
+            ws = self._ws
+        a = 0 if begin else head
+        b = T - (self.K - 1) if end else T - tail
+        nb = (b - a + 7) // 8
+        if out is None:
+            out = t.empty((n_streams, nb), dtype=t.uint8, device=self.device)
+        elif (out.dtype != t.uint8 or not out.is_cuda or out.dim() != 2 or out.shape[0] != n_streams or out.shape[1] < nb
+              or out.stride(1) != 1 or (n_streams > 1 and out.stride(0) < nb)):
+            raise ValueError(f"out must be a uint8 CUDA tensor of [{n_streams}][>= {nb}] with contiguous rows")
+        n_bits = C.c_size_t(0)
+        _lib.check(_lib.load().vit_hip_decode_streams(
+            self._handle._h, C.c_void_p(symbols.data_ptr()), n_streams, pitch, T, window, head, tail, flags, C.c_void_p(ws.data_ptr()),
+            ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()), out.stride(0) if n_streams > 1 else nb,
+            C.byref(n_bits), self._stream()))
+        return out[:, :nb], int(n_bits.value)
+
     def depuncture(self, punctured, mask, out=None):
         """Depuncturing front-end (examples/helpers/puncture_code_helpers.h:17-55) for a batch: `punctured` is the device
         tensor [F][P] of transmitted symbols, `mask` the puncturing vector over one whole frame (truthy = transmitted, one
@@ -710,6 +759,94 @@ class StreamDecoder:
         self.calls.append((self._pending.shape[0], self._first, True))
         self._done = True
         self._pending = None
+        return self._emit(out, n_bits, True)
+
+
+class MultiStreamDecoder:
+    """The lockstep counterpart of StreamDecoder on top of BatchDecoder.decode_streams: push() the same number of steps of each of
+    n_streams streams as they arrive, get one `bytes` per stream back; finish() ends all streams (their last K-1 steps are the
+    zero tail).
+
+    The pending symbols of all streams live in ONE device buffer [n_streams][pitch][R] whose pitch is rounded up to a multiple of
+    the window (and grown when a push needs it), so every internal call reads them in place on one shared window grid.  Every
+    internal call is a segment of head + n*window + tail steps (one uniform batch), BEGIN on the first, under the hold-back rule
+    of StreamDecoder: pushes of ANY sizes plus finish() give, per stream, exactly the bits of ONE decode_stream call over that
+    whole stream.  Whole bytes only, as there; `n_bits` counts the bits returned so far per stream."""
+
+    def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None):
+        self.decoder = decoder
+        self.n_streams = int(n_streams)
+        self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
+        seg = self.head + self.window + self.tail
+        pitch = -(-seg // self.window) * self.window
+        if self.n_streams < 1 or decoder.streams_workspace_bytes(self.n_streams, pitch, seg, True, False, self.window, self.head,
+                                                                 self.tail) == 0:
+            raise ValueError("n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams")
+        self.n_bits = 0
+        self.calls = []                       # (steps, begin, end) of every internal call, for inspection
+        self._first = True
+        self._done = False
+        self._buf = None                      # device tensor [n_streams][pitch][R], pitch % window == 0
+        self._pending = 0                     # steps of it in use, per stream
+        self._carry = np.zeros((self.n_streams, 0), dtype=np.uint8)
+
+    def _append(self, symbols):
+        if symbols is None:
+            return
+        t, R = self.decoder.torch, self.decoder.R
+        want = t.int16 if self.decoder.soft_bytes == 2 else t.int8
+        if (symbols.dtype != want or not symbols.is_cuda or symbols.dim() < 2 or symbols.shape[0] != self.n_streams
+                or symbols[0].numel() % R != 0):
+            raise ValueError(f"symbols must be a {want} CUDA tensor of [n_streams][steps][R]")
+        symbols = symbols.reshape(self.n_streams, -1, R)
+        P, n = self._pending, symbols.shape[1]
+        if self._buf is None or P + n > self._buf.shape[1]:
+            # room for what is held back between calls as well, so that a steady flow of pushes of this size does not grow it again
+            pitch = -(-(P + n + self.head + 2 * self.window + self.tail) // self.window) * self.window
+            buf = t.empty((self.n_streams, pitch, R), dtype=want, device=self.decoder.device)
+            if P:
+                buf[:, :P] = self._buf[:, :P]
+            self._buf = buf
+        self._buf[:, P:P + n] = symbols
+        self._pending = P + n
+
+    def _emit(self, out, n_bits, final):
+        bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
+        keep = bits.shape[1] if final else bits.shape[1] - bits.shape[1] % 8
+        self._carry = bits[:, keep:]
+        self.n_bits += keep
+        return [np.packbits(row[:keep], bitorder="big").tobytes() for row in bits]
+
+    def push(self, symbols) -> list:
+        if self._done:
+            raise RuntimeError("the streams are finished")
+        self._append(symbols)
+        P = self._pending
+        hold = self.head + self.window + self.decoder.K - 1
+        if P < hold + self.window:
+            return [b""] * self.n_streams
+        n = (P - hold) // self.window
+        T = self.head + n * self.window + self.tail
+        out, n_bits = self.decoder.decode_streams(self._buf, T, self._first, False, self.window, self.head, self.tail)
+        self.calls.append((T, self._first, False))
+        data = self._emit(out, n_bits, False)
+        keep = P - n * self.window
+        self._buf[:, :keep] = self._buf[:, n * self.window:P].clone()
+        self._pending = keep
+        self._first = False
+        return data
+
+    def finish(self, symbols=None) -> list:
+        if self._done:
+            raise RuntimeError("the streams are finished")
+        self._append(symbols)
+        if self._buf is None:
+            raise ValueError("empty streams")
+        out, n_bits = self.decoder.decode_streams(self._buf, self._pending, self._first, True, self.window, self.head, self.tail)
+        self.calls.append((self._pending, self._first, True))
+        self._done = True
+        self._buf = None
+        self._pending = 0
         return self._emit(out, n_bits, True)
 
 
