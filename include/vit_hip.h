@@ -42,6 +42,9 @@
  *   vit_hip_synth_batch       the BER harness's frame generator   examples/run_snr_ber.cpp:311-359,
  *                             examples/helpers/test_helpers.h:17-64, convolutional_encoder_shift_register.h:42-62
  *   vit_hip_count_bit_errors  get_total_bit_errors()              examples/helpers/test_helpers.h:95-104
+ *   vit_hip_encode_batch      ConvolutionalEncoder_ShiftRegister / _Lookup   include/viterbi/convolutional_encoder_shift_register.h:42-62,
+ *                             convolutional_encoder_lookup.h, for a batch on the caller's bytes (start state, tail-biting, strides)
+ *   vit_hip_channel_errors_batch  no reference counterpart: the re-encoded channel symbol error count (rule below)
  *
  * Semantics are those of the reference SCALAR strategy (strict '>' decision, wrapping error_t arithmetic,
  * renormalise only when new_metric[0] >= threshold): SURVEY.md section 8(a').  All results are bit-exact.
@@ -478,6 +481,48 @@ int vit_hip_synth_batch(vit_hip_handle h, size_t frames, size_t L, uint64_t seed
 /* *d_count (uint64, device) += number of differing bits between two device byte arrays. */
 int vit_hip_count_bit_errors(vit_hip_handle h, const uint8_t* d_a, const uint8_t* d_b, size_t n_bytes, uint64_t* d_count,
                              vit_hip_stream_t stream);
+
+/* ---- re-encoding decoded bits on the device: batched encoder and channel symbol error count --------------------------------
+ * The decode calls return bytes and nothing about the channel.  The standard measure is the re-encoded channel symbol error rate:
+ * encode the decoded bits again, compare with the hard decisions of the received symbols, skip erasures (the FIC / MSC BER a DAB
+ * receiver shows; what CCSDS / DVB-S node synchronisation minimises over symbol alignment, puncture phase and inversion; what an
+ * LTE PDCCH blind decoder ranks its candidates by).  vit_hip_encode_batch is the reference's encoder
+ * (include/viterbi/convolutional_encoder_shift_register.h:42-62, convolutional_encoder_lookup.h) for a batch, on the caller's own
+ * bytes; vit_hip_channel_errors_batch re-encodes in registers and counts, so neither the symbols nor an encoded copy leave the
+ * card or are written.  Rule, with the handle's K, R, polynomials (vit_hip_info.polynomials) and soft_decision_high / low:
+ *   - shape: steps = L + (TAIL ? K-1 : 0) trellis steps per frame, R symbols per step.  Without TAIL the frame is an unterminated
+ *     piece of a stream.  Info bit t of a frame is bit 7 - t%8 of byte t/8 (MSB-first, as chainback() writes them); the pad bits
+ *     of the last byte are not read as data;
+ *   - state numbering is the decoder's -- what d_start_state of vit_hip_update_batch and d_end_state of vit_hip_chainback_batch
+ *     mean: bit j of a state, 0 <= j < K-1, is the input bit j+1 steps back.  The register at step t is
+ *     (state << 1 | bit_t) & (2^K - 1), and symbol i of step t is parity(reg & G[i]): soft_decision_high for 1, _low for 0;
+ *   - start state: d_start_state[f], NULL => 0.  Under TAIL_BITING bit j of the start state is info bit L-1-j (the state the
+ *     frame's last K-1 bits leave).  d_end_state_out [frames] may be NULL; it receives the state after the last step (0 under TAIL);
+ *   - strides are in elements, as in vit_hip_update_batch_resume: frame f's symbols start at f * symbol_frame_stride soft_t
+ *     elements (0 => steps*R), its bytes at f * bytes_frame_stride (0 => ceil(L/8)); a non-zero stride is at least that value.
+ *     What lies between two frames is neither read nor written;
+ *   - layouts: frames = 1 with flags = 0 and a start state is one segment of vit_hip_decode_stream; frames = n_streams with
+ *     symbol_frame_stride = pitch*R and bytes_frame_stride = out_pitch_bytes is vit_hip_decode_streams.  The caller passes
+ *     d_symbols + a*R, the first emitted step, and carries the last K-1 emitted bits as the next call's start state;
+ *   - counts, per frame, uint32: d_compared[f] = symbols r with 2 r != high + low -- a symbol at the midpoint is an erasure (the 0
+ *     vit_hip_depuncture_batch inserts, or a noisy symbol that lands there) and is skipped; d_errors[f] = compared symbols whose
+ *     hard decision 2 r > high + low differs from the re-encoded bit.  d_errors is required, d_compared may be NULL.  The call
+ *     OVERWRITES both (it zeroes them on `stream`, then adds integer partial sums: the result does not depend on order).
+ * Errors: VIT_HIP_ERR_UNSUPPORTED when vit_hip_info.table_is_linear is 0.  VIT_HIP_ERR_INVALID_ARG, with nothing launched and the
+ * outputs untouched, for a NULL required pointer, L = 0, both flags, unknown flag bits, TAIL_BITING with L < K or a non-NULL
+ * d_start_state, a stride that is too small, steps*R >= 2^32 (and int16 symbols at an odd address, or more than 2^32 - 1 frames).
+ * frames = 0 returns VIT_HIP_OK with no work.
+ * Batch calls like the others: they only enqueue on `stream` (encode: one launch; channel errors: the memsets and one launch),
+ * allocate nothing, synchronise nothing, can be captured into a hipGraph, read the handle and write only caller buffers. */
+#define VIT_HIP_ENCODE_TAIL        1u  /* K-1 zero bits follow the L info bits: steps = L + K-1 */
+#define VIT_HIP_ENCODE_TAIL_BITING 2u  /* start state = the state the frame's last K-1 bits leave; steps = L; d_start_state must be NULL */
+int vit_hip_encode_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_frame_stride, size_t frames, size_t L,
+                         unsigned flags, const uint32_t* d_start_state, void* d_symbols_out, size_t symbol_frame_stride,
+                         uint32_t* d_end_state_out, vit_hip_stream_t stream);
+int vit_hip_channel_errors_batch(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_stride, const uint8_t* d_bytes,
+                                 size_t bytes_frame_stride, size_t frames, size_t L, unsigned flags,
+                                 const uint32_t* d_start_state, uint32_t* d_errors, uint32_t* d_compared,
+                                 vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

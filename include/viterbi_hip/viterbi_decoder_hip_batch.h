@@ -127,6 +127,21 @@ public:
     void count_bit_errors(const uint8_t* d_a, const uint8_t* d_b, size_t n_bytes, uint64_t* d_count, void* stream = nullptr) {
         check(vit_hip_count_bit_errors(m_hip, d_a, d_b, n_bytes, d_count, stream), "vit_hip_count_bit_errors");
     }
+    // the encoder on the caller's own bytes (vit_hip_encode_batch) and the re-encoded channel symbol error count of decoded bytes
+    // against the received symbols (vit_hip_channel_errors_batch): flags VIT_HIP_ENCODE_TAIL / _TAIL_BITING or 0 (a piece of a
+    // stream), strides in elements (0: packed), states in the decoder's numbering; d_errors / d_compared [frames] are overwritten
+    void encode(const uint8_t* d_bytes, size_t frames, size_t total_bits, soft_t* d_symbols_out, unsigned flags = VIT_HIP_ENCODE_TAIL,
+                const uint32_t* d_start_state = nullptr, uint32_t* d_end_state_out = nullptr, size_t bytes_frame_stride = 0,
+                size_t symbol_frame_stride = 0, void* stream = nullptr) {
+        check(vit_hip_encode_batch(m_hip, d_bytes, bytes_frame_stride, frames, total_bits, flags, d_start_state, d_symbols_out,
+                                   symbol_frame_stride, d_end_state_out, stream), "vit_hip_encode_batch");
+    }
+    void channel_errors(const soft_t* d_symbols, const uint8_t* d_bytes, size_t frames, size_t total_bits, uint32_t* d_errors,
+                        uint32_t* d_compared = nullptr, unsigned flags = VIT_HIP_ENCODE_TAIL, const uint32_t* d_start_state = nullptr,
+                        size_t symbol_frame_stride = 0, size_t bytes_frame_stride = 0, void* stream = nullptr) {
+        check(vit_hip_channel_errors_batch(m_hip, d_symbols, symbol_frame_stride, d_bytes, bytes_frame_stride, frames, total_bits,
+                                           flags, d_start_state, d_errors, d_compared, stream), "vit_hip_channel_errors_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

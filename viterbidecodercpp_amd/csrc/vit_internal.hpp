@@ -6,6 +6,7 @@
 //   vit_pipeline.hip vit_hip_pipeline_* and its schedule rules (no kernel of its own)
 //   vit_host.hip     the single-decoder host route and the frame route (kernels_one.hpp)
 //   vit_tools.hip    synth, bit-error count, shader clock, kernel listing, precompile, RCCL table broadcast (kernels_synth.hpp)
+//   vit_encode.hip   the encoder on the caller's bytes and the re-encoded channel symbol error count (kernels_enc.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -668,6 +668,99 @@ class BatchDecoder:
                                                         a.numel(), C.c_void_p(count.data_ptr()), self._stream()))
         return count
 
+    def _encode_args(self, bytes, L, tail, tail_biting, start_state, bytes_frame_stride=0):
+        """(frames, flags, steps, byte stride, start-state tensor or None) of an encode / channel_errors call"""
+        t = self.torch
+        if tail_biting and start_state is not None:
+            raise ValueError("a tail-biting frame takes its start state from its own last K-1 bits")
+        flags = _lib.ENCODE_TAIL_BITING if tail_biting else (_lib.ENCODE_TAIL if tail else 0)
+        steps = L + (self.K - 1 if flags == _lib.ENCODE_TAIL else 0)
+        nb = (L + 7) // 8
+        if bytes.dtype != t.uint8 or not bytes.is_cuda or bytes.dim() not in (1, 2) or bytes.stride(-1) != 1:
+            raise ValueError("bytes must be a uint8 CUDA tensor [frames][>= ceil(L/8)] (or one frame's bytes) with contiguous rows")
+        if bytes.dim() == 2:
+            frames = int(bytes.shape[0])
+            stride = int(bytes_frame_stride) or (int(bytes.stride(0)) if frames > 1 else int(bytes.shape[1]))
+            if bytes.shape[1] < nb:
+                raise ValueError(f"{L} bits need {nb} bytes per frame")
+        else:
+            stride = int(bytes_frame_stride) or nb
+            frames = (bytes.numel() - nb) // stride + 1 if bytes.numel() >= nb else 0
+        if frames < 1 or stride < nb:
+            raise ValueError(f"bytes holds no frame of {nb} bytes at stride {stride}")
+        ss = None
+        if start_state is not None:
+            ss = t.as_tensor(start_state, dtype=t.int32, device=self.device).reshape(-1).contiguous()
+            if ss.numel() != frames:
+                raise ValueError("start_state must hold one state per frame")
+        return frames, flags, steps, stride, ss
+
+    def encode(self, bytes, L: int, tail=True, tail_biting=False, start_state=None, out=None, end_state_out=False):
+        """the convolutional encoder on device-resident info bytes (vit_hip_encode_batch): bytes [F][>= ceil(L/8)] uint8, MSB-first
+        as chainback() writes them -> symbols [F][steps][R] at exactly soft_decision_high / low, steps = L + K-1 with `tail`
+        (K-1 zero bits follow), L with tail=False (an unterminated piece of a stream, from `start_state` [F], None = 0) or with
+        `tail_biting` (the frame starts in the state its last K-1 bits leave).  States are numbered as update()'s start_state
+        and chainback()'s end_state.  `out`: a symbol tensor of steps*R elements per frame, or a 2-D one [F][>= steps*R] whose
+        row stride is the frame stride (what lies behind steps*R is left as it is).  end_state_out: True (or an int32 tensor [F])
+        returns (symbols, end_state): the state after each frame's last step."""
+        t = self.torch
+        frames, flags, steps, bstride, ss = self._encode_args(bytes, L, tail, tail_biting, start_state)
+        sdt = t.int16 if self.soft_bytes == 2 else t.int8
+        n = steps * self.R
+        if out is None:
+            out = t.empty((frames, steps, self.R), dtype=sdt, device=self.device)
+        if out.dtype != sdt or not out.is_cuda:
+            raise ValueError(f"out must be a {sdt} CUDA tensor")
+        if out.is_contiguous() and out.numel() == frames * n:
+            sstride = n
+        elif out.dim() == 2 and out.shape[0] == frames and out.shape[1] >= n and out.stride(1) == 1 and (frames == 1 or out.stride(0) >= n):
+            sstride = int(out.stride(0)) if frames > 1 else n
+        else:
+            raise ValueError(f"out must hold {frames} x {n} symbols, or be [frames][>= {n}] with contiguous rows")
+        es = None
+        if end_state_out is not False and end_state_out is not None:
+            es = t.empty(frames, dtype=t.int32, device=self.device) if end_state_out is True else end_state_out
+            if es.dtype != t.int32 or not es.is_cuda or not es.is_contiguous() or es.numel() != frames:
+                raise ValueError(f"end_state_out must be a contiguous int32 CUDA tensor of {frames} elements")
+        _lib.check(_lib.load().vit_hip_encode_batch(
+            self._handle._h, C.c_void_p(bytes.data_ptr()), bstride, frames, L, flags, C.c_void_p(ss.data_ptr()) if ss is not None else None,
+            C.c_void_p(out.data_ptr()), sstride, C.c_void_p(es.data_ptr()) if es is not None else None, self._stream()))
+        return (out, es) if es is not None else out
+
+    def channel_errors(self, symbols, bytes, L: int, tail=True, tail_biting=False, start_state=None, symbol_frame_stride: int = 0,
+                       bytes_frame_stride: int = 0):
+        """the re-encoded channel symbol error count (vit_hip_channel_errors_batch): the decoded `bytes` [F][>= ceil(L/8)] are
+        encoded again in registers (tail / tail_biting / start_state as encode()) and compared with the hard decisions of the
+        received `symbols`.  returns (errors, compared), int32 device tensors [F]: compared = symbols that are not at the
+        midpoint (high + low)/2 -- erasures, such as the 0 depuncture() inserts, are skipped --, errors = compared symbols whose
+        hard decision differs from the re-encoded bit.  errors / compared is the channel symbol error rate.
+        symbols: frame f's [steps][R] start at element f * symbol_frame_stride of the tensor (0: the row stride of a [F][...]
+        tensor, else packed); it may be a view into a larger buffer.  bytes_frame_stride likewise (0: the row stride)."""
+        t = self.torch
+        frames, flags, steps, bstride, ss = self._encode_args(bytes, L, tail, tail_biting, start_state, bytes_frame_stride)
+        sdt = t.int16 if self.soft_bytes == 2 else t.int8
+        n = steps * self.R
+        if symbols.dtype != sdt or not symbols.is_cuda or symbols.stride(-1) != 1:
+            raise ValueError(f"symbols must be a {sdt} CUDA tensor whose last dimension is contiguous")
+        sstride = int(symbol_frame_stride)
+        if sstride == 0:
+            if symbols.is_contiguous() and symbols.numel() == frames * n:
+                sstride = n
+            elif symbols.dim() >= 2 and symbols.shape[0] == frames and symbols[0].is_contiguous() and symbols[0].numel() >= n:
+                sstride = int(symbols.stride(0)) if frames > 1 else n
+            else:
+                raise ValueError(f"symbols must hold {frames} x {n} symbols, or pass symbol_frame_stride")
+        room = symbols.untyped_storage().nbytes() // symbols.element_size() - symbols.storage_offset()
+        if sstride < n or room < (frames - 1) * sstride + n:
+            raise ValueError(f"{frames} frames of {n} symbols at stride {sstride} do not fit the symbol tensor")
+        err = t.empty(frames, dtype=t.int32, device=self.device)
+        cmp = t.empty(frames, dtype=t.int32, device=self.device)
+        _lib.check(_lib.load().vit_hip_channel_errors_batch(
+            self._handle._h, C.c_void_p(symbols.data_ptr()), sstride, C.c_void_p(bytes.data_ptr()), bstride, frames, L, flags,
+            C.c_void_p(ss.data_ptr()) if ss is not None else None, C.c_void_p(err.data_ptr()), C.c_void_p(cmp.data_ptr()),
+            self._stream()))
+        return err, cmp
+
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The
         workspace is an array of independent slabs of `workspace_tile_frames` frames (vit_hip_info), so `frames` frames
@@ -692,6 +785,14 @@ class BatchDecoder:
         return dec
 
 
+def _next_states(states, bits, K):
+    """decoder states [n] after the input bits [n][n_bits] (0/1) have been shifted in: bit j = the input bit j+1 steps back"""
+    states = np.asarray(states, dtype=np.int64).copy()
+    for j in range(max(bits.shape[1] - (K - 1), 0), bits.shape[1]):
+        states = (states << 1) | bits[:, j].astype(np.int64)
+    return states & ((1 << (K - 1)) - 1)
+
+
 class StreamDecoder:
     """A chunked receiver on top of BatchDecoder.decode_stream: push() symbols of one long stream as they arrive, get decoded
     bytes back; finish() ends the stream (its last K-1 steps are the zero tail).
@@ -701,13 +802,22 @@ class StreamDecoder:
     lead-in and this one's look-ahead) and at least one more window (window + K-1 steps), so that the final segment under END
     always holds a full window -- with that, pushes of ANY sizes plus finish() decode to exactly the bits of ONE decode_stream
     call over the whole stream (tests/test_stream_cpu.py: chunked vs one call).  Whole bytes only: the sub-byte remainder is
-    carried to the next call; finish() pads the last byte with zeros.  `n_bits` counts the bits returned so far."""
+    carried to the next call; finish() pads the last byte with zeros.  `n_bits` counts the bits returned so far.
 
-    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None):
+    channel_errors=True: the object also keeps `.channel_errors`, the running (errors, compared) of the re-encoded channel symbol
+    error count (BatchDecoder.channel_errors) over every trellis step whose bit has been emitted so far -- each step exactly once,
+    however the pushes were cut; finish() adds the K-1 tail steps.  One more launch and one small read-back per internal call; the
+    last K-1 emitted bits are carried as the next call's start state.  Off (the default), nothing changes."""
+
+    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False):
         self.decoder = decoder
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
         if decoder.stream_workspace_bytes(self.head + self.window + self.tail, True, False, self.window, self.head, self.tail) == 0:
             raise ValueError("window, head, tail outside the argument rule of vit_hip_decode_stream")
+        self._count_errors = bool(channel_errors)
+        if self._count_errors:
+            self.channel_errors = (0, 0)
+            self._state = np.zeros(1, dtype=np.int64)    # the last K-1 emitted bits, as a decoder state
         self.n_bits = 0
         self.calls = []                       # (steps, begin, end) of every internal call, for inspection
         self._first = True
@@ -724,6 +834,14 @@ class StreamDecoder:
             raise ValueError(f"symbols must be a {want} CUDA tensor of [steps][R]")
         symbols = symbols.reshape(-1, self.decoder.R)
         self._pending = symbols.contiguous() if self._pending is None else t.cat([self._pending, symbols])
+
+    def _count(self, symbols, out, n_bits, end):
+        """symbols: the segment from its first emitted step on; out: the n_bits bits the call emitted"""
+        dec = self.decoder
+        steps = n_bits + (dec.K - 1 if end else 0)
+        err, cmp = dec.channel_errors(symbols, out, n_bits, tail=end, start_state=self._state, symbol_frame_stride=steps * dec.R)
+        self.channel_errors = (self.channel_errors[0] + int(err.item()), self.channel_errors[1] + int(cmp.item()))
+        self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy())[None, :n_bits], dec.K)
 
     def _emit(self, out, n_bits, final):
         bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy())[:n_bits]])
@@ -744,6 +862,8 @@ class StreamDecoder:
         T = self.head + n * self.window + self.tail
         out, n_bits = self.decoder.decode_stream(self._pending[:T], self._first, False, self.window, self.head, self.tail)
         self.calls.append((T, self._first, False))
+        if self._count_errors:
+            self._count(self._pending[0 if self._first else self.head:], out, n_bits, False)
         data = self._emit(out, n_bits, False)
         self._pending = self._pending[n * self.window:].contiguous()
         self._first = False
@@ -757,6 +877,8 @@ class StreamDecoder:
             raise ValueError("an empty stream")
         out, n_bits = self.decoder.decode_stream(self._pending, self._first, True, self.window, self.head, self.tail)
         self.calls.append((self._pending.shape[0], self._first, True))
+        if self._count_errors:
+            self._count(self._pending[0 if self._first else self.head:], out, n_bits, True)
         self._done = True
         self._pending = None
         return self._emit(out, n_bits, True)
@@ -771,9 +893,13 @@ class MultiStreamDecoder:
     the window (and grown when a push needs it), so every internal call reads them in place on one shared window grid.  Every
     internal call is a segment of head + n*window + tail steps (one uniform batch), BEGIN on the first, under the hold-back rule
     of StreamDecoder: pushes of ANY sizes plus finish() give, per stream, exactly the bits of ONE decode_stream call over that
-    whole stream.  Whole bytes only, as there; `n_bits` counts the bits returned so far per stream."""
+    whole stream.  Whole bytes only, as there; `n_bits` counts the bits returned so far per stream.
 
-    def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None):
+    channel_errors=True: `.channel_errors` holds two int64 arrays of length n_streams, the running (errors, compared) per stream, as
+    StreamDecoder's -- one launch and one read-back per internal call for all streams."""
+
+    def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
+                 channel_errors: bool = False):
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
@@ -789,6 +915,18 @@ class MultiStreamDecoder:
         self._buf = None                      # device tensor [n_streams][pitch][R], pitch % window == 0
         self._pending = 0                     # steps of it in use, per stream
         self._carry = np.zeros((self.n_streams, 0), dtype=np.uint8)
+        self._count_errors = bool(channel_errors)
+        if self._count_errors:
+            self.channel_errors = (np.zeros(self.n_streams, dtype=np.int64), np.zeros(self.n_streams, dtype=np.int64))
+            self._state = np.zeros(self.n_streams, dtype=np.int64)
+
+    def _count(self, first_step, out, n_bits, end):
+        """first_step: the segment's first emitted step; out [n_streams][ceil(n_bits/8)]: the bits the call emitted"""
+        dec = self.decoder
+        err, cmp = dec.channel_errors(self._buf[:, first_step:], out, n_bits, tail=end, start_state=self._state,
+                                      symbol_frame_stride=self._buf.shape[1] * dec.R)
+        self.channel_errors = (self.channel_errors[0] + err.cpu().numpy(), self.channel_errors[1] + cmp.cpu().numpy())
+        self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits], dec.K)
 
     def _append(self, symbols):
         if symbols is None:
@@ -829,6 +967,8 @@ class MultiStreamDecoder:
         T = self.head + n * self.window + self.tail
         out, n_bits = self.decoder.decode_streams(self._buf, T, self._first, False, self.window, self.head, self.tail)
         self.calls.append((T, self._first, False))
+        if self._count_errors:
+            self._count(0 if self._first else self.head, out, n_bits, False)
         data = self._emit(out, n_bits, False)
         keep = P - n * self.window
         self._buf[:, :keep] = self._buf[:, n * self.window:P].clone()
@@ -844,6 +984,8 @@ class MultiStreamDecoder:
             raise ValueError("empty streams")
         out, n_bits = self.decoder.decode_streams(self._buf, self._pending, self._first, True, self.window, self.head, self.tail)
         self.calls.append((self._pending, self._first, True))
+        if self._count_errors:
+            self._count(0 if self._first else self.head, out, n_bits, True)
         self._done = True
         self._buf = None
         self._pending = 0

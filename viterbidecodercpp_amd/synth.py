@@ -63,6 +63,25 @@ def encode_tail_biting_numpy(K: int, R: int, G, bits: np.ndarray) -> np.ndarray:
     return out
 
 
+def channel_errors_numpy(code, high: int, low: int, symbols: np.ndarray, coded_bits: np.ndarray):
+    """numpy mirror of the counting rule of vit_hip_channel_errors_batch: symbols [F][steps][R] received, coded_bits the same
+    shape (0/1), the decoded bits encoded again.  returns (errors [F], compared [F]) int64: compared = symbols r with
+    2 r != high + low (a symbol at the midpoint is an erasure and is skipped), errors = compared symbols whose hard decision
+    2 r > high + low differs from the re-encoded bit."""
+    sym = np.asarray(symbols)
+    if sym.ndim < 2:
+        sym = sym.reshape(1, -1)
+    F = sym.shape[0]
+    twice = 2 * sym.reshape(F, -1).astype(np.int64)
+    coded = np.asarray(coded_bits).reshape(F, -1) != 0
+    if twice.shape != coded.shape or twice.shape[1] % code.R != 0:
+        raise ValueError("symbols and coded_bits must both be [frames][steps][R]")
+    mid = int(high) + int(low)
+    compared = twice != mid
+    errors = compared & ((twice > mid) != coded)
+    return errors.sum(axis=1).astype(np.int64), compared.sum(axis=1).astype(np.int64)
+
+
 def _round_half_away(x):
     return np.sign(x) * np.floor(np.abs(x) + np.float32(0.5))
 
