@@ -88,13 +88,13 @@ public:
     // windows of `window` steps (0: 1024) with `head` steps of lead-in and `tail` of look-ahead (0: the default 8*(K-1)); begin /
     // end: the segment holds the encoder's start / the zero tail.  Returns the number of bits written to d_bytes_out, MSB-first.
     size_t stream_workspace_bytes(size_t steps, bool begin, bool end, size_t window = 0, size_t head = 0, size_t tail = 0) const {
-        return vit_hip_stream_workspace_bytes(m_hip, steps, window ? window : 1024, extension(head), extension(tail),
+        return vit_hip_stream_workspace_bytes(m_hip, steps, window_or_default(window), extension(head), extension(tail),
                                               stream_flags(begin, end));
     }
     size_t decode_stream(const soft_t* d_symbols, size_t steps, bool begin, bool end, void* d_workspace, size_t workspace_size,
                          uint8_t* d_bytes_out, size_t window = 0, size_t head = 0, size_t tail = 0, void* stream = nullptr) {
         size_t n_bits = 0;
-        check(vit_hip_decode_stream(m_hip, d_symbols, steps, window ? window : 1024, extension(head), extension(tail),
+        check(vit_hip_decode_stream(m_hip, d_symbols, steps, window_or_default(window), extension(head), extension(tail),
                                     stream_flags(begin, end), d_workspace, workspace_size, d_bytes_out, &n_bits, stream),
               "vit_hip_decode_stream");
         return n_bits;
@@ -104,14 +104,14 @@ public:
     // is what decode_stream returns for stream s.  Defaults as decode_stream.  Returns the number of bits written to each row.
     size_t streams_workspace_bytes(size_t n_streams, size_t pitch, size_t steps, bool begin, bool end, size_t window = 0,
                                    size_t head = 0, size_t tail = 0) const {
-        return vit_hip_streams_workspace_bytes(m_hip, n_streams, pitch, steps, window ? window : 1024, extension(head), extension(tail),
+        return vit_hip_streams_workspace_bytes(m_hip, n_streams, pitch, steps, window_or_default(window), extension(head), extension(tail),
                                                stream_flags(begin, end));
     }
     size_t decode_streams(const soft_t* d_symbols, size_t n_streams, size_t pitch, size_t steps, bool begin, bool end, void* d_workspace,
                           size_t workspace_size, uint8_t* d_bytes_out, size_t out_pitch_bytes, size_t window = 0, size_t head = 0,
                           size_t tail = 0, void* stream = nullptr) {
         size_t n_bits = 0;
-        check(vit_hip_decode_streams(m_hip, d_symbols, n_streams, pitch, steps, window ? window : 1024, extension(head), extension(tail),
+        check(vit_hip_decode_streams(m_hip, d_symbols, n_streams, pitch, steps, window_or_default(window), extension(head), extension(tail),
                                      stream_flags(begin, end), d_workspace, workspace_size, d_bytes_out, out_pitch_bytes, &n_bits,
                                      stream),
               "vit_hip_decode_streams");
@@ -157,6 +157,7 @@ public:
 
 private:
     static size_t extension(size_t steps) { return steps ? steps : 8 * (K - 1); }
+    static size_t window_or_default(size_t window) { return window ? window : 1024; }
     static unsigned stream_flags(bool begin, bool end) { return (begin ? VIT_HIP_STREAM_BEGIN : 0u) | (end ? VIT_HIP_STREAM_END : 0u); }
     static void check(int rc, const char* what) {
         if (rc != VIT_HIP_OK) {

@@ -276,6 +276,45 @@ def test_stream_decoder_ragged_pushes(oracle, code_id, decode_type, W, head, tai
             assert len(sd.calls) > 2
 
 
+def test_stream_decoder_input_forms(oracle):
+    """push() / finish() take flat tensors, [n][R] tensors and [n][R] views that are not contiguous; every form passes through the
+    receiver's pitched buffer.  First a piece under one window, then one of several windows (the buffer grows while steps are
+    pending), then pieces whose step counts are no multiples of 8; the L % 8 = 5 last bits leave through the carry at finish()"""
+    import torch
+
+    code = COMMON_CODES[2]
+    pc, table, config = make_table_config(code, "SOFT16")
+    dec = BatchDecoder(table, config)
+    W, head, tail, L = 64, 48, 48, 20 * 64 + 5
+    bits, sym = make_stream(code, pc, L, 3.0, seed=31)
+    T = sym.shape[0]
+    d_sym = torch.from_numpy(sym).cuda()
+
+    def spaced(x):                                     # every other row of a tensor twice as long
+        wide = torch.full((2 * x.shape[0], code.R), 0x55, dtype=x.dtype, device=x.device)
+        wide[::2] = x
+        return wide[::2]
+
+    forms = (lambda x: x.reshape(-1), lambda x: x, spaced)
+    sizes = [40, 300, 131, 203, 77, 333]
+    sizes.append(T - sum(sizes))
+    assert sizes[0] < W and sizes[1] > 4 * W and sizes[-1] > 0 and all(n % 8 for n in sizes[2:])
+    sd = StreamDecoder(dec, W, head, tail)
+    data, pos = b"", 0
+    for k, n in enumerate(sizes):
+        piece = forms[k % 3](d_sym[pos:pos + n])
+        assert piece.is_contiguous() == (k % 3 != 2)
+        data += sd.finish(piece) if k == len(sizes) - 1 else sd.push(piece)
+        if k == 0:
+            assert data == b""
+        pos += n
+    assert sd.n_bits == L and isinstance(sd.n_bits, int) and len(data) == (L + 7) // 8
+    one, n_one = dec.decode_stream(d_sym, True, True, W, head, tail)
+    assert n_one == L and data == one.cpu().numpy().tobytes()
+    want, want_n = stream_reference(oracle, code, oracle_cfg("SOFT16", code.R), sym, W, head, tail, BEGIN | END)
+    assert want_n == L and data == want.tobytes(), sd.calls
+
+
 def test_punctured_stream_composition(oracle):
     """K = 7 R = 1/2 punctured to 3/4 (mask 1 1 0 1 1 0 over three steps), depunctured by vit_hip_depuncture_batch with frames =
     the number of puncturing periods into the contiguous [T][R] stream, then decoded: bit-exact against the restatement on the

@@ -743,7 +743,8 @@ const char* streams_invalid(vit_hip_handle h, size_t n_streams, size_t pitch, si
     return nullptr;
 }
 
-void stream_layout(vit_hip_handle h, StreamLayout& o) {
+// fills the workspace layout of `o` and returns its size
+size_t stream_layout(vit_hip_handle h, StreamLayout& o) {
     const size_t K1 = (size_t)h->K - 1, row = (size_t)h->N * (size_t)h->error_bytes;
     o.L_u = o.S_u - K1;
     o.nbe_u = (o.L_u + 7) / 8;
@@ -758,7 +759,7 @@ void stream_layout(vit_hip_handle h, StreamLayout& o) {
     o.bytes_u = o.end_r + align_up(o.rows_r * sizeof(uint32_t), 256);
     // 16 bytes of slack behind each: the stitch kernel's loads stay inside the rows, this keeps them off the next part anyway
     o.bytes_r = o.bytes_u + align_up(o.rows_u * o.nbe_u + 16, 256);
-    o.total = o.bytes_r + align_up(o.rows_r * o.nbe_r + 16, 256);
+    return o.total = o.bytes_r + align_up(o.rows_r * o.nbe_r + 16, 256);
 }
 
 // the launches of both entry points, once the arguments have passed.  pitch and out_pitch: unused with one stream
@@ -860,13 +861,25 @@ int decode_streams_launch(vit_hip_handle h, const StreamLayout& lay, const void*
     if (vit::stream_launch_stitch(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream stitch launch failed");
     return VIT_HIP_OK;
 }
+
+// what both decode entry points do once their argument rule has passed: pointer, layout and workspace checks, the launches, n_bits_out
+int decode_streams_checked(vit_hip_handle h, StreamLayout& lay, const void* d_symbols, size_t pitch, size_t W, size_t head, unsigned flags,
+                           void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, size_t out_pitch, size_t* n_bits_out,
+                           vit_hip_stream_t stream) {
+    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
+    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    if (workspace_bytes < stream_layout(h, lay)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
+    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    const int rc = decode_streams_launch(h, lay, d_symbols, pitch, W, head, flags, d_workspace, d_bytes_out, out_pitch, stream);
+    if (rc != VIT_HIP_OK) return rc;
+    if (n_bits_out) *n_bits_out = lay.b - lay.a;
+    return VIT_HIP_OK;
+}
 }  // namespace
 
 size_t vit_hip_stream_workspace_bytes(vit_hip_handle h, size_t T, size_t W, size_t head, size_t tail, unsigned flags) {
     StreamLayout lay;
-    if (!h || stream_invalid(h, T, W, head, tail, flags, lay)) return 0;
-    stream_layout(h, lay);
-    return lay.total;
+    return !h || stream_invalid(h, T, W, head, tail, flags, lay) ? 0 : stream_layout(h, lay);
 }
 
 int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
@@ -875,23 +888,13 @@ int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, siz
     if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
     StreamLayout lay;
     if (const char* why = stream_invalid(h, T, W, head, tail, flags, lay)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
-    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
-    stream_layout(h, lay);
-    if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    const int rc = decode_streams_launch(h, lay, d_symbols, 0, W, head, flags, d_workspace, d_bytes_out, 0, stream);
-    if (rc != VIT_HIP_OK) return rc;
-    if (n_bits_out) *n_bits_out = lay.b - lay.a;
-    return VIT_HIP_OK;
+    return decode_streams_checked(h, lay, d_symbols, 0, W, head, flags, d_workspace, workspace_bytes, d_bytes_out, 0, n_bits_out, stream);
 }
 
 size_t vit_hip_streams_workspace_bytes(vit_hip_handle h, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head, size_t tail,
                                        unsigned flags) {
     StreamLayout lay;
-    if (!h || streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay)) return 0;
-    stream_layout(h, lay);
-    return lay.total;
+    return !h || streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay) ? 0 : stream_layout(h, lay);
 }
 
 int vit_hip_decode_streams(vit_hip_handle h, const void* d_symbols, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head,
@@ -901,15 +904,8 @@ int vit_hip_decode_streams(vit_hip_handle h, const void* d_symbols, size_t n_str
     StreamLayout lay;
     if (const char* why = streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
     if (out_pitch_bytes < (lay.b - lay.a + 7) / 8) return fail(VIT_HIP_ERR_INVALID_ARG, "out_pitch_bytes shorter than ceil(n_out/8)");
-    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
-    stream_layout(h, lay);
-    if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    const int rc = decode_streams_launch(h, lay, d_symbols, pitch, W, head, flags, d_workspace, d_bytes_out, out_pitch_bytes, stream);
-    if (rc != VIT_HIP_OK) return rc;
-    if (n_bits_out) *n_bits_out = lay.b - lay.a;
-    return VIT_HIP_OK;
+    return decode_streams_checked(h, lay, d_symbols, pitch, W, head, flags, d_workspace, workspace_bytes, d_bytes_out, out_pitch_bytes,
+                                  n_bits_out, stream);
 }
 
 static int vit_hip_get_kernel_resources_impl(vit_hip_handle h, int kernel, vit_hip_kernel_resources* out) {

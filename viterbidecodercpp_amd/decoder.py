@@ -293,6 +293,11 @@ class ViterbiDecoder_HIP:
         return rs + base.take_unreported_renormalisation()
 
 
+def _ptr(x):
+    """the address a tensor starts at, as the C ABI takes it; NULL for None"""
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
 class BatchDecoder:
     """Frame-parallel decoder on device-resident torch tensors (vit_hip_*_batch).  torch is plumbing only: it owns the
     HBM buffers and the stream."""
@@ -310,6 +315,8 @@ class BatchDecoder:
         i = self._handle.info
         self.K, self.R, self.N, self.W = i.K, i.R, i.num_states, i.decision_words
         self.soft_bytes, self.error_bytes = i.soft_bytes, i.error_bytes
+        self._soft_dtype = torch.int16 if self.soft_bytes == 2 else torch.int8
+        self._error_dtype = torch.int16 if self.error_bytes == 2 else torch.uint8     # int16 carries the uint16 bit pattern
         self._ws = None
 
     @property
@@ -329,7 +336,10 @@ class BatchDecoder:
         return _lib.load().vit_hip_workspace_bytes(self._handle._h, frames, L)
 
     def _workspace(self, frames, L, workspace=None):
-        need = self.workspace_bytes(frames, L)
+        return self._scratch(self.workspace_bytes(frames, L), workspace)
+
+    def _scratch(self, need, workspace=None):
+        """the caller's workspace once it has passed the size and alignment check, else the decoder's own, grown to `need` bytes"""
         if workspace is not None:
             if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
                 raise ValueError("workspace too small or not 256-byte aligned")
@@ -354,11 +364,12 @@ class BatchDecoder:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _is_symbols(self, symbols):
+        return symbols.dtype == self._soft_dtype and symbols.is_cuda and symbols.is_contiguous()
+
     def _check_symbols(self, symbols, n_steps):
-        t = self.torch
-        want = t.int16 if self.soft_bytes == 2 else t.int8
-        if symbols.dtype != want or not symbols.is_cuda or not symbols.is_contiguous():
-            raise ValueError(f"symbols must be a contiguous {want} CUDA tensor")
+        if not self._is_symbols(symbols):
+            raise ValueError(f"symbols must be a contiguous {self._soft_dtype} CUDA tensor")
         frames = symbols.shape[0]
         if symbols.numel() != frames * n_steps * self.R:
             raise ValueError("symbols must have shape [frames][n_steps][R]")
@@ -372,32 +383,27 @@ class BatchDecoder:
         n_steps = (L + self.K - 1) if n_steps is None else n_steps
         frames = self._check_symbols(symbols, n_steps)
         ws = self._workspace(frames, L, workspace)
-        edt = t.int16 if self.error_bytes == 2 else t.uint8  # int16 carries the uint16 bit pattern
         met, rs = metrics_out, renorm_out
         if want_metrics:
-            met = t.empty((frames, self.N), dtype=edt, device=self.device) if met is None else met
+            met = t.empty((frames, self.N), dtype=self._error_dtype, device=self.device) if met is None else met
             rs = t.empty(frames, dtype=t.int64, device=self.device) if rs is None else rs
         ss = None
         if start_state is not None:
             ss = t.as_tensor(start_state, dtype=t.int32, device=self.device).contiguous()
         _lib.check(_lib.load().vit_hip_update_batch(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), frames, n_steps, L, C.c_void_p(ws.data_ptr()),
-            ws.numel() * ws.element_size(),
-            C.c_void_p(met.data_ptr()) if met is not None else None, C.c_void_p(rs.data_ptr()) if rs is not None else None,
-            C.c_void_p(ss.data_ptr()) if ss is not None else None, self._stream()))
+            self._handle._h, _ptr(symbols), frames, n_steps, L, _ptr(ws), ws.numel() * ws.element_size(), _ptr(met), _ptr(rs), _ptr(ss),
+            self._stream()))
         return met, rs
 
     def reset_batch(self, frames: int, start_state=None, metrics_out=None):
         """ViterbiDecoder_Core::reset for every frame (core.h:202-211): the device-resident metrics [F][N] a streamed decode
         starts from."""
         t = self.torch
-        edt = t.int16 if self.error_bytes == 2 else t.uint8
-        met = t.empty((frames, self.N), dtype=edt, device=self.device) if metrics_out is None else metrics_out
+        met = t.empty((frames, self.N), dtype=self._error_dtype, device=self.device) if metrics_out is None else metrics_out
         ss = None
         if start_state is not None:
             ss = t.as_tensor(start_state, dtype=t.int32, device=self.device).contiguous()
-        _lib.check(_lib.load().vit_hip_reset_batch(self._handle._h, frames, C.c_void_p(ss.data_ptr()) if ss is not None else None,
-                                                   C.c_void_p(met.data_ptr()), self._stream()))
+        _lib.check(_lib.load().vit_hip_reset_batch(self._handle._h, frames, _ptr(ss), _ptr(met), self._stream()))
         return met
 
     def update_resume(self, symbols, L: int, first_step: int, metrics, n_steps: int = None, symbol_frame_stride: int = 0,
@@ -411,9 +417,8 @@ class BatchDecoder:
         frames = metrics.shape[0]
         if n_steps is None:
             n_steps = symbols.shape[1]
-        want = t.int16 if self.soft_bytes == 2 else t.int8
-        if symbols.dtype != want or not symbols.is_cuda:
-            raise ValueError(f"symbols must be a {want} CUDA tensor")
+        if symbols.dtype != self._soft_dtype or not symbols.is_cuda:
+            raise ValueError(f"symbols must be a {self._soft_dtype} CUDA tensor")
         if symbol_frame_stride == 0 and not symbols.is_contiguous():
             raise ValueError("packed chunks must be contiguous (or pass symbol_frame_stride)")
         if metrics.dim() != 2 or metrics.shape[1] != self.N or not metrics.is_contiguous():
@@ -428,9 +433,8 @@ class BatchDecoder:
         ws = self._workspace(frames, L, workspace)
         rs = t.empty(frames, dtype=t.int64, device=self.device) if renorm_out is None else renorm_out
         _lib.check(_lib.load().vit_hip_update_batch_resume(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), symbol_frame_stride, frames, first_step, n_steps, L,
-            C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(), C.c_void_p(metrics.data_ptr()),
-            C.c_void_p(rs.data_ptr()), self._stream()))
+            self._handle._h, _ptr(symbols), symbol_frame_stride, frames, first_step, n_steps, L, _ptr(ws), ws.numel() * ws.element_size(),
+            _ptr(metrics), _ptr(rs), self._stream()))
         return rs
 
     def chainback(self, frames: int, L: int, end_state=None, out=None, workspace=None, kernel=None):
@@ -443,13 +447,11 @@ class BatchDecoder:
         es = None
         if end_state is not None:
             es = t.as_tensor(end_state, dtype=t.int32, device=self.device).contiguous()
-        esp = C.c_void_p(es.data_ptr()) if es is not None else None
         if kernel is None:
-            _lib.check(_lib.load().vit_hip_chainback_batch(self._handle._h, C.c_void_p(ws.data_ptr()), frames, L,
-                                                           C.c_void_p(out.data_ptr()), esp, self._stream()))
+            _lib.check(_lib.load().vit_hip_chainback_batch(self._handle._h, _ptr(ws), frames, L, _ptr(out), _ptr(es), self._stream()))
         else:
-            _lib.check(_lib.load().vit_hip_chainback_batch_ex(self._handle._h, C.c_void_p(ws.data_ptr()), frames, L,
-                                                              C.c_void_p(out.data_ptr()), esp, self._stream(), int(kernel)))
+            _lib.check(_lib.load().vit_hip_chainback_batch_ex(self._handle._h, _ptr(ws), frames, L, _ptr(out), _ptr(es), self._stream(),
+                                                              int(kernel)))
         return out
 
     def decode(self, symbols, L: int, out=None, want_metrics=False):
@@ -459,13 +461,10 @@ class BatchDecoder:
         ws = self._workspace(frames, L)
         if out is None:
             out = t.empty((frames, (L + 7) // 8), dtype=t.uint8, device=self.device)
-        edt = t.int16 if self.error_bytes == 2 else t.uint8  # int16 carries the uint16 bit pattern
-        met = t.empty((frames, self.N), dtype=edt, device=self.device) if want_metrics else None
+        met = t.empty((frames, self.N), dtype=self._error_dtype, device=self.device) if want_metrics else None
         rs = t.empty(frames, dtype=t.int64, device=self.device) if want_metrics else None
         _lib.check(_lib.load().vit_hip_decode_batch(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), frames, L, C.c_void_p(ws.data_ptr()), ws.numel(),
-            C.c_void_p(out.data_ptr()), C.c_void_p(met.data_ptr()) if met is not None else None,
-            C.c_void_p(rs.data_ptr()) if rs is not None else None, None, self._stream()))
+            self._handle._h, _ptr(symbols), frames, L, _ptr(ws), ws.numel(), _ptr(out), _ptr(met), _ptr(rs), None, self._stream()))
         return (out, met, rs) if want_metrics else out
 
     def tail_biting_workspace_bytes(self, frames: int, L: int, head: int = None, tail: int = None) -> int:
@@ -489,15 +488,7 @@ class BatchDecoder:
         need = self.tail_biting_workspace_bytes(frames, L, head, tail)
         if need == 0:
             raise ValueError(f"tail-biting decoding needs L >= K and head, tail >= K-1 (K = {self.K})")
-        if workspace is not None:
-            if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
-                raise ValueError("workspace too small or not 256-byte aligned")
-            ws = workspace
-        else:
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
-            ws = self._ws
+        ws = self._scratch(need, workspace)
         if out is None:
             out = t.empty((frames, (L + 7) // 8), dtype=t.uint8, device=self.device)
         want_extra = end_state_out is not None or ok_out is not None
@@ -511,16 +502,27 @@ class BatchDecoder:
             if x is not None and (x.dtype != dt or not x.is_cuda or not x.is_contiguous() or x.numel() != n):
                 raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor of {n} elements")
         _lib.check(_lib.load().vit_hip_decode_tail_biting_batch(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), frames, L, head, tail, C.c_void_p(ws.data_ptr()),
-            ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()),
-            C.c_void_p(end_state_out.data_ptr()) if want_extra else None, C.c_void_p(ok_out.data_ptr()) if want_extra else None,
-            self._stream()))
+            self._handle._h, _ptr(symbols), frames, L, head, tail, _ptr(ws), ws.numel() * ws.element_size(), _ptr(out), _ptr(end_state_out),
+            _ptr(ok_out), self._stream()))
         return (out, end_state_out, ok_out) if want_extra else out
 
     def _stream_args(self, window, head, tail, begin, end):
         head, tail = self._tb_extension(head, tail)
         window = 1024 if window is None else int(window)
         return window, head, tail, (_lib.STREAM_BEGIN if begin else 0) | (_lib.STREAM_END if end else 0)
+
+    def _emitted(self, T, head, tail, begin, end):
+        """(a, b, bytes): a segment of T steps emits the bits of its steps [a, b), in ceil((b - a)/8) bytes"""
+        a = 0 if begin else head
+        b = T - (self.K - 1) if end else T - tail
+        return a, b, (b - a + 7) // 8
+
+    def _segment(self, need, workspace, T, head, tail, begin, end, rule):
+        """what decode_stream and decode_streams share behind their symbol checks: the verdict of the argument rule (need = 0: outside
+        it, `rule` says what it asks), the scratch workspace and the bytes one stream's segment emits"""
+        if need == 0:
+            raise ValueError(rule)
+        return self._scratch(need, workspace), self._emitted(T, head, tail, begin, end)[2]
 
     def stream_workspace_bytes(self, steps: int, begin=True, end=False, window: int = None, head: int = None, tail: int = None) -> int:
         window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
@@ -536,34 +538,21 @@ class BatchDecoder:
         steps run as one uniform batch."""
         t = self.torch
         window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
-        want = t.int16 if self.soft_bytes == 2 else t.int8
-        if symbols.dtype != want or not symbols.is_cuda or not symbols.is_contiguous() or symbols.numel() % self.R != 0:
-            raise ValueError(f"symbols must be a contiguous {want} CUDA tensor of [steps][R]")
+        if not self._is_symbols(symbols) or symbols.numel() % self.R != 0:
+            raise ValueError(f"symbols must be a contiguous {self._soft_dtype} CUDA tensor of [steps][R]")
         T = symbols.numel() // self.R
         need = _lib.load().vit_hip_stream_workspace_bytes(self._handle._h, T, window, head, tail, flags)
-        if need == 0:
-            raise ValueError(f"stream decoding needs head, tail >= K-1, window >= 8, head, tail, and a segment that emits bits "
-                             f"(K = {self.K}, steps = {T}, window = {window}, head = {head}, tail = {tail})")
-        if workspace is not None:
-            if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
-                raise ValueError("workspace too small or not 256-byte aligned")
-            ws = workspace
-        else:
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
-            ws = self._ws
-        a = 0 if begin else head
-        b = T - (self.K - 1) if end else T - tail
-        nb = (b - a + 7) // 8
+        ws, nb = self._segment(need, workspace, T, head, tail, begin, end,
+                               f"stream decoding needs head, tail >= K-1, window >= 8, head, tail, and a segment that emits bits "
+                               f"(K = {self.K}, steps = {T}, window = {window}, head = {head}, tail = {tail})")
         if out is None:
             out = t.empty(nb, dtype=t.uint8, device=self.device)
         elif out.dtype != t.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != nb:
             raise ValueError(f"out must be a contiguous uint8 CUDA tensor of {nb} elements")
         n_bits = C.c_size_t(0)
         _lib.check(_lib.load().vit_hip_decode_stream(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), T, window, head, tail, flags, C.c_void_p(ws.data_ptr()),
-            ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()), C.byref(n_bits), self._stream()))
+            self._handle._h, _ptr(symbols), T, window, head, tail, flags, _ptr(ws), ws.numel() * ws.element_size(), _ptr(out),
+            C.byref(n_bits), self._stream()))
         return out, int(n_bits.value)
 
     def streams_workspace_bytes(self, n_streams: int, pitch: int, steps: int, begin=True, end=False, window: int = None,
@@ -581,28 +570,15 @@ class BatchDecoder:
         ceil(n_bits/8) are left as they are and the view of the written part is returned."""
         t = self.torch
         window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
-        want = t.int16 if self.soft_bytes == 2 else t.int8
-        if symbols.dtype != want or not symbols.is_cuda or not symbols.is_contiguous() or symbols.dim() != 3 or symbols.shape[2] != self.R:
-            raise ValueError(f"symbols must be a contiguous {want} CUDA tensor of [n_streams][pitch][R]")
+        if not self._is_symbols(symbols) or symbols.dim() != 3 or symbols.shape[2] != self.R:
+            raise ValueError(f"symbols must be a contiguous {self._soft_dtype} CUDA tensor of [n_streams][pitch][R]")
         n_streams, pitch = int(symbols.shape[0]), int(symbols.shape[1])
         T = pitch if steps is None else int(steps)
         need = _lib.load().vit_hip_streams_workspace_bytes(self._handle._h, n_streams, pitch, T, window, head, tail, flags)
-        if need == 0:
-            raise ValueError(f"decoding lockstep streams needs what decode_stream needs, n_streams >= 1, pitch >= steps and pitch a "
-                             f"multiple of the window (K = {self.K}, n_streams = {n_streams}, pitch = {pitch}, steps = {T}, "
-                             f"window = {window}, head = {head}, tail = {tail})")
-        if workspace is not None:
-            if workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 256 != 0:
-                raise ValueError("workspace too small or not 256-byte aligned")
-            ws = workspace
-        else:
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
-            ws = self._ws
-        a = 0 if begin else head
-        b = T - (self.K - 1) if end else T - tail
-        nb = (b - a + 7) // 8
+        ws, nb = self._segment(need, workspace, T, head, tail, begin, end,
+                               f"decoding lockstep streams needs what decode_stream needs, n_streams >= 1, pitch >= steps and pitch a "
+                               f"multiple of the window (K = {self.K}, n_streams = {n_streams}, pitch = {pitch}, steps = {T}, "
+                               f"window = {window}, head = {head}, tail = {tail})")
         if out is None:
             out = t.empty((n_streams, nb), dtype=t.uint8, device=self.device)
         elif (out.dtype != t.uint8 or not out.is_cuda or out.dim() != 2 or out.shape[0] != n_streams or out.shape[1] < nb
@@ -610,9 +586,8 @@ class BatchDecoder:
             raise ValueError(f"out must be a uint8 CUDA tensor of [{n_streams}][>= {nb}] with contiguous rows")
         n_bits = C.c_size_t(0)
         _lib.check(_lib.load().vit_hip_decode_streams(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), n_streams, pitch, T, window, head, tail, flags, C.c_void_p(ws.data_ptr()),
-            ws.numel() * ws.element_size(), C.c_void_p(out.data_ptr()), out.stride(0) if n_streams > 1 else nb,
-            C.byref(n_bits), self._stream()))
+            self._handle._h, _ptr(symbols), n_streams, pitch, T, window, head, tail, flags, _ptr(ws), ws.numel() * ws.element_size(),
+            _ptr(out), out.stride(0) if n_streams > 1 else nb, C.byref(n_bits), self._stream()))
         return out[:, :nb], int(n_bits.value)
 
     def depuncture(self, punctured, mask, out=None):
@@ -625,8 +600,7 @@ class BatchDecoder:
             raise ValueError("the puncturing vector must cover whole trellis steps (a multiple of R symbols)")
         if not (punctured.is_cuda and punctured.dim() == 2 and punctured.is_contiguous()):
             raise ValueError("punctured symbols must be a contiguous [frames][P] device tensor")
-        sdt = t.int16 if self.soft_bytes == 2 else t.int8
-        if punctured.dtype != sdt or punctured.shape[1] != int(mask.sum()):
+        if punctured.dtype != self._soft_dtype or punctured.shape[1] != int(mask.sum()):
             raise ValueError("punctured symbols: wrong dtype or count for this puncturing vector")
         key = mask.tobytes()
         cached = getattr(self, "_depuncture_map", None)
@@ -637,10 +611,9 @@ class BatchDecoder:
         d_idx = cached[1]
         frames = punctured.shape[0]
         if out is None:
-            out = t.empty((frames, mask.size // self.R, self.R), dtype=sdt, device=self.device)
-        _lib.check(_lib.load().vit_hip_depuncture_batch(self._handle._h, C.c_void_p(punctured.data_ptr()), punctured.shape[1],
-                                                        C.c_void_p(d_idx.data_ptr()), mask.size, frames,
-                                                        C.c_void_p(out.data_ptr()), self._stream()))
+            out = t.empty((frames, mask.size // self.R, self.R), dtype=self._soft_dtype, device=self.device)
+        _lib.check(_lib.load().vit_hip_depuncture_batch(self._handle._h, _ptr(punctured), punctured.shape[1], _ptr(d_idx), mask.size,
+                                                        frames, _ptr(out), self._stream()))
         return out
 
     def synth(self, frames: int, L: int, ebn0_db, seed: int = 1, first_frame: int = 0, tx_out=None, symbols_out=None):
@@ -648,12 +621,11 @@ class BatchDecoder:
         reference BER harness's generator, examples/run_snr_ber.cpp:311-359).  ebn0_db=None: noise-free symbols at exactly
         high / low.  returns (tx_bytes [F][L/8] uint8, symbols [F][L+K-1][R] soft dtype), both on the device."""
         t = self.torch
-        sdt = t.int16 if self.soft_bytes == 2 else t.int8
         tx = t.empty((frames, L // 8), dtype=t.uint8, device=self.device) if tx_out is None else tx_out
-        sym = t.empty((frames, L + self.K - 1, self.R), dtype=sdt, device=self.device) if symbols_out is None else symbols_out
+        sym = t.empty((frames, L + self.K - 1, self.R), dtype=self._soft_dtype, device=self.device) if symbols_out is None else symbols_out
         _lib.check(_lib.load().vit_hip_synth_batch(self._handle._h, frames, L, int(seed), int(first_frame),
                                                    0.0 if ebn0_db is None else float(ebn0_db), 1 if ebn0_db is None else 0,
-                                                   C.c_void_p(tx.data_ptr()), C.c_void_p(sym.data_ptr()), self._stream()))
+                                                   _ptr(tx), _ptr(sym), self._stream()))
         return tx, sym
 
     def count_bit_errors(self, a, b, count=None):
@@ -664,8 +636,7 @@ class BatchDecoder:
             raise ValueError("need two contiguous uint8 tensors of equal size")
         if count is None:
             count = t.zeros(1, dtype=t.int64, device=self.device)
-        _lib.check(_lib.load().vit_hip_count_bit_errors(self._handle._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                                        a.numel(), C.c_void_p(count.data_ptr()), self._stream()))
+        _lib.check(_lib.load().vit_hip_count_bit_errors(self._handle._h, _ptr(a), _ptr(b), a.numel(), _ptr(count), self._stream()))
         return count
 
     def _encode_args(self, bytes, L, tail, tail_biting, start_state, bytes_frame_stride=0):
@@ -705,12 +676,11 @@ class BatchDecoder:
         returns (symbols, end_state): the state after each frame's last step."""
         t = self.torch
         frames, flags, steps, bstride, ss = self._encode_args(bytes, L, tail, tail_biting, start_state)
-        sdt = t.int16 if self.soft_bytes == 2 else t.int8
         n = steps * self.R
         if out is None:
-            out = t.empty((frames, steps, self.R), dtype=sdt, device=self.device)
-        if out.dtype != sdt or not out.is_cuda:
-            raise ValueError(f"out must be a {sdt} CUDA tensor")
+            out = t.empty((frames, steps, self.R), dtype=self._soft_dtype, device=self.device)
+        if out.dtype != self._soft_dtype or not out.is_cuda:
+            raise ValueError(f"out must be a {self._soft_dtype} CUDA tensor")
         if out.is_contiguous() and out.numel() == frames * n:
             sstride = n
         elif out.dim() == 2 and out.shape[0] == frames and out.shape[1] >= n and out.stride(1) == 1 and (frames == 1 or out.stride(0) >= n):
@@ -723,8 +693,7 @@ class BatchDecoder:
             if es.dtype != t.int32 or not es.is_cuda or not es.is_contiguous() or es.numel() != frames:
                 raise ValueError(f"end_state_out must be a contiguous int32 CUDA tensor of {frames} elements")
         _lib.check(_lib.load().vit_hip_encode_batch(
-            self._handle._h, C.c_void_p(bytes.data_ptr()), bstride, frames, L, flags, C.c_void_p(ss.data_ptr()) if ss is not None else None,
-            C.c_void_p(out.data_ptr()), sstride, C.c_void_p(es.data_ptr()) if es is not None else None, self._stream()))
+            self._handle._h, _ptr(bytes), bstride, frames, L, flags, _ptr(ss), _ptr(out), sstride, _ptr(es), self._stream()))
         return (out, es) if es is not None else out
 
     def channel_errors(self, symbols, bytes, L: int, tail=True, tail_biting=False, start_state=None, symbol_frame_stride: int = 0,
@@ -738,10 +707,9 @@ class BatchDecoder:
         tensor, else packed); it may be a view into a larger buffer.  bytes_frame_stride likewise (0: the row stride)."""
         t = self.torch
         frames, flags, steps, bstride, ss = self._encode_args(bytes, L, tail, tail_biting, start_state, bytes_frame_stride)
-        sdt = t.int16 if self.soft_bytes == 2 else t.int8
         n = steps * self.R
-        if symbols.dtype != sdt or not symbols.is_cuda or symbols.stride(-1) != 1:
-            raise ValueError(f"symbols must be a {sdt} CUDA tensor whose last dimension is contiguous")
+        if symbols.dtype != self._soft_dtype or not symbols.is_cuda or symbols.stride(-1) != 1:
+            raise ValueError(f"symbols must be a {self._soft_dtype} CUDA tensor whose last dimension is contiguous")
         sstride = int(symbol_frame_stride)
         if sstride == 0:
             if symbols.is_contiguous() and symbols.numel() == frames * n:
@@ -756,8 +724,7 @@ class BatchDecoder:
         err = t.empty(frames, dtype=t.int32, device=self.device)
         cmp = t.empty(frames, dtype=t.int32, device=self.device)
         _lib.check(_lib.load().vit_hip_channel_errors_batch(
-            self._handle._h, C.c_void_p(symbols.data_ptr()), sstride, C.c_void_p(bytes.data_ptr()), bstride, frames, L, flags,
-            C.c_void_p(ss.data_ptr()) if ss is not None else None, C.c_void_p(err.data_ptr()), C.c_void_p(cmp.data_ptr()),
+            self._handle._h, _ptr(symbols), sstride, _ptr(bytes), bstride, frames, L, flags, _ptr(ss), _ptr(err), _ptr(cmp),
             self._stream()))
         return err, cmp
 
@@ -780,216 +747,8 @@ class BatchDecoder:
         else:
             ws = self._workspace(frames, L, workspace)
         dec = t.empty((frames, n_steps, self.W), dtype=t.int64, device=self.device)
-        _lib.check(_lib.load().vit_hip_export_decisions(self._handle._h, C.c_void_p(ws.data_ptr()), frames, n_steps, L,
-                                                        C.c_void_p(dec.data_ptr()), self._stream()))
+        _lib.check(_lib.load().vit_hip_export_decisions(self._handle._h, _ptr(ws), frames, n_steps, L, _ptr(dec), self._stream()))
         return dec
-
-
-def _next_states(states, bits, K):
-    """decoder states [n] after the input bits [n][n_bits] (0/1) have been shifted in: bit j = the input bit j+1 steps back"""
-    states = np.asarray(states, dtype=np.int64).copy()
-    for j in range(max(bits.shape[1] - (K - 1), 0), bits.shape[1]):
-        states = (states << 1) | bits[:, j].astype(np.int64)
-    return states & ((1 << (K - 1)) - 1)
-
-
-class StreamDecoder:
-    """A chunked receiver on top of BatchDecoder.decode_stream: push() symbols of one long stream as they arrive, get decoded
-    bytes back; finish() ends the stream (its last K-1 steps are the zero tail).
-
-    Every internal call is a segment of head + n*window + tail steps on the window grid (one uniform batch), BEGIN on the first.
-    What does not fill a window yet stays on the device: the last head + tail steps of the segment just decoded (the next one's
-    lead-in and this one's look-ahead) and at least one more window (window + K-1 steps), so that the final segment under END
-    always holds a full window -- with that, pushes of ANY sizes plus finish() decode to exactly the bits of ONE decode_stream
-    call over the whole stream (tests/test_stream_cpu.py: chunked vs one call).  Whole bytes only: the sub-byte remainder is
-    carried to the next call; finish() pads the last byte with zeros.  `n_bits` counts the bits returned so far.
-
-    channel_errors=True: the object also keeps `.channel_errors`, the running (errors, compared) of the re-encoded channel symbol
-    error count (BatchDecoder.channel_errors) over every trellis step whose bit has been emitted so far -- each step exactly once,
-    however the pushes were cut; finish() adds the K-1 tail steps.  One more launch and one small read-back per internal call; the
-    last K-1 emitted bits are carried as the next call's start state.  Off (the default), nothing changes."""
-
-    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False):
-        self.decoder = decoder
-        self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
-        if decoder.stream_workspace_bytes(self.head + self.window + self.tail, True, False, self.window, self.head, self.tail) == 0:
-            raise ValueError("window, head, tail outside the argument rule of vit_hip_decode_stream")
-        self._count_errors = bool(channel_errors)
-        if self._count_errors:
-            self.channel_errors = (0, 0)
-            self._state = np.zeros(1, dtype=np.int64)    # the last K-1 emitted bits, as a decoder state
-        self.n_bits = 0
-        self.calls = []                       # (steps, begin, end) of every internal call, for inspection
-        self._first = True
-        self._done = False
-        self._pending = None                  # device tensor [steps][R]
-        self._carry = np.zeros(0, dtype=np.uint8)
-
-    def _append(self, symbols):
-        if symbols is None:
-            return
-        t = self.decoder.torch
-        want = t.int16 if self.decoder.soft_bytes == 2 else t.int8
-        if symbols.dtype != want or not symbols.is_cuda or symbols.numel() % self.decoder.R != 0:
-            raise ValueError(f"symbols must be a {want} CUDA tensor of [steps][R]")
-        symbols = symbols.reshape(-1, self.decoder.R)
-        self._pending = symbols.contiguous() if self._pending is None else t.cat([self._pending, symbols])
-
-    def _count(self, symbols, out, n_bits, end):
-        """symbols: the segment from its first emitted step on; out: the n_bits bits the call emitted"""
-        dec = self.decoder
-        steps = n_bits + (dec.K - 1 if end else 0)
-        err, cmp = dec.channel_errors(symbols, out, n_bits, tail=end, start_state=self._state, symbol_frame_stride=steps * dec.R)
-        self.channel_errors = (self.channel_errors[0] + int(err.item()), self.channel_errors[1] + int(cmp.item()))
-        self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy())[None, :n_bits], dec.K)
-
-    def _emit(self, out, n_bits, final):
-        bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy())[:n_bits]])
-        keep = bits.size if final else bits.size - bits.size % 8
-        self._carry = bits[keep:]
-        self.n_bits += keep
-        return np.packbits(bits[:keep], bitorder="big").tobytes()
-
-    def push(self, symbols) -> bytes:
-        if self._done:
-            raise RuntimeError("the stream is finished")
-        self._append(symbols)
-        P = 0 if self._pending is None else self._pending.shape[0]
-        hold = self.head + self.window + self.decoder.K - 1
-        if P < hold + self.window:
-            return b""
-        n = (P - hold) // self.window
-        T = self.head + n * self.window + self.tail
-        out, n_bits = self.decoder.decode_stream(self._pending[:T], self._first, False, self.window, self.head, self.tail)
-        self.calls.append((T, self._first, False))
-        if self._count_errors:
-            self._count(self._pending[0 if self._first else self.head:], out, n_bits, False)
-        data = self._emit(out, n_bits, False)
-        self._pending = self._pending[n * self.window:].contiguous()
-        self._first = False
-        return data
-
-    def finish(self, symbols=None) -> bytes:
-        if self._done:
-            raise RuntimeError("the stream is finished")
-        self._append(symbols)
-        if self._pending is None:
-            raise ValueError("an empty stream")
-        out, n_bits = self.decoder.decode_stream(self._pending, self._first, True, self.window, self.head, self.tail)
-        self.calls.append((self._pending.shape[0], self._first, True))
-        if self._count_errors:
-            self._count(self._pending[0 if self._first else self.head:], out, n_bits, True)
-        self._done = True
-        self._pending = None
-        return self._emit(out, n_bits, True)
-
-
-class MultiStreamDecoder:
-    """The lockstep counterpart of StreamDecoder on top of BatchDecoder.decode_streams: push() the same number of steps of each of
-    n_streams streams as they arrive, get one `bytes` per stream back; finish() ends all streams (their last K-1 steps are the
-    zero tail).
-
-    The pending symbols of all streams live in ONE device buffer [n_streams][pitch][R] whose pitch is rounded up to a multiple of
-    the window (and grown when a push needs it), so every internal call reads them in place on one shared window grid.  Every
-    internal call is a segment of head + n*window + tail steps (one uniform batch), BEGIN on the first, under the hold-back rule
-    of StreamDecoder: pushes of ANY sizes plus finish() give, per stream, exactly the bits of ONE decode_stream call over that
-    whole stream.  Whole bytes only, as there; `n_bits` counts the bits returned so far per stream.
-
-    channel_errors=True: `.channel_errors` holds two int64 arrays of length n_streams, the running (errors, compared) per stream, as
-    StreamDecoder's -- one launch and one read-back per internal call for all streams."""
-
-    def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
-                 channel_errors: bool = False):
-        self.decoder = decoder
-        self.n_streams = int(n_streams)
-        self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
-        seg = self.head + self.window + self.tail
-        pitch = -(-seg // self.window) * self.window
-        if self.n_streams < 1 or decoder.streams_workspace_bytes(self.n_streams, pitch, seg, True, False, self.window, self.head,
-                                                                 self.tail) == 0:
-            raise ValueError("n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams")
-        self.n_bits = 0
-        self.calls = []                       # (steps, begin, end) of every internal call, for inspection
-        self._first = True
-        self._done = False
-        self._buf = None                      # device tensor [n_streams][pitch][R], pitch % window == 0
-        self._pending = 0                     # steps of it in use, per stream
-        self._carry = np.zeros((self.n_streams, 0), dtype=np.uint8)
-        self._count_errors = bool(channel_errors)
-        if self._count_errors:
-            self.channel_errors = (np.zeros(self.n_streams, dtype=np.int64), np.zeros(self.n_streams, dtype=np.int64))
-            self._state = np.zeros(self.n_streams, dtype=np.int64)
-
-    def _count(self, first_step, out, n_bits, end):
-        """first_step: the segment's first emitted step; out [n_streams][ceil(n_bits/8)]: the bits the call emitted"""
-        dec = self.decoder
-        err, cmp = dec.channel_errors(self._buf[:, first_step:], out, n_bits, tail=end, start_state=self._state,
-                                      symbol_frame_stride=self._buf.shape[1] * dec.R)
-        self.channel_errors = (self.channel_errors[0] + err.cpu().numpy(), self.channel_errors[1] + cmp.cpu().numpy())
-        self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits], dec.K)
-
-    def _append(self, symbols):
-        if symbols is None:
-            return
-        t, R = self.decoder.torch, self.decoder.R
-        want = t.int16 if self.decoder.soft_bytes == 2 else t.int8
-        if (symbols.dtype != want or not symbols.is_cuda or symbols.dim() < 2 or symbols.shape[0] != self.n_streams
-                or symbols[0].numel() % R != 0):
-            raise ValueError(f"symbols must be a {want} CUDA tensor of [n_streams][steps][R]")
-        symbols = symbols.reshape(self.n_streams, -1, R)
-        P, n = self._pending, symbols.shape[1]
-        if self._buf is None or P + n > self._buf.shape[1]:
-            # room for what is held back between calls as well, so that a steady flow of pushes of this size does not grow it again
-            pitch = -(-(P + n + self.head + 2 * self.window + self.tail) // self.window) * self.window
-            buf = t.empty((self.n_streams, pitch, R), dtype=want, device=self.decoder.device)
-            if P:
-                buf[:, :P] = self._buf[:, :P]
-            self._buf = buf
-        self._buf[:, P:P + n] = symbols
-        self._pending = P + n
-
-    def _emit(self, out, n_bits, final):
-        bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
-        keep = bits.shape[1] if final else bits.shape[1] - bits.shape[1] % 8
-        self._carry = bits[:, keep:]
-        self.n_bits += keep
-        return [np.packbits(row[:keep], bitorder="big").tobytes() for row in bits]
-
-    def push(self, symbols) -> list:
-        if self._done:
-            raise RuntimeError("the streams are finished")
-        self._append(symbols)
-        P = self._pending
-        hold = self.head + self.window + self.decoder.K - 1
-        if P < hold + self.window:
-            return [b""] * self.n_streams
-        n = (P - hold) // self.window
-        T = self.head + n * self.window + self.tail
-        out, n_bits = self.decoder.decode_streams(self._buf, T, self._first, False, self.window, self.head, self.tail)
-        self.calls.append((T, self._first, False))
-        if self._count_errors:
-            self._count(0 if self._first else self.head, out, n_bits, False)
-        data = self._emit(out, n_bits, False)
-        keep = P - n * self.window
-        self._buf[:, :keep] = self._buf[:, n * self.window:P].clone()
-        self._pending = keep
-        self._first = False
-        return data
-
-    def finish(self, symbols=None) -> list:
-        if self._done:
-            raise RuntimeError("the streams are finished")
-        self._append(symbols)
-        if self._buf is None:
-            raise ValueError("empty streams")
-        out, n_bits = self.decoder.decode_streams(self._buf, self._pending, self._first, True, self.window, self.head, self.tail)
-        self.calls.append((self._pending, self._first, True))
-        if self._count_errors:
-            self._count(0 if self._first else self.head, out, n_bits, True)
-        self._done = True
-        self._buf = None
-        self._pending = 0
-        return self._emit(out, n_bits, True)
 
 
 class DecodePipeline:
@@ -1030,9 +789,7 @@ class DecodePipeline:
         if after_current_stream:
             self._inputs_ready.record(t.cuda.current_stream(self.decoder.device))
             _lib.check(L.vit_hip_pipeline_wait_event(self._p, C.c_void_p(self._inputs_ready.cuda_event)))
-        _lib.check(L.vit_hip_pipeline_submit(self._p, C.c_void_p(symbols.data_ptr()), frames, C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(end_state.data_ptr()) if end_state is not None else None,
-                                             C.c_void_p(self._done.cuda_event)))
+        _lib.check(L.vit_hip_pipeline_submit(self._p, _ptr(symbols), frames, _ptr(out), _ptr(end_state), C.c_void_p(self._done.cuda_event)))
 
     def wait_done(self, stream=None):
         """order `stream` (default: torch's current stream) behind every batch submitted so far, without blocking the host:
@@ -1054,8 +811,7 @@ class DecodePipeline:
         _lib.check(_lib.load().vit_hip_pipeline_last_workspace(self._p, C.byref(ws), C.byref(f0), C.byref(nf)))
         n = nf.value if frames is None else min(frames, nf.value)
         out = t.empty((n, n_steps, dec.W), dtype=t.int64, device=dec.device)
-        _lib.check(_lib.load().vit_hip_export_decisions(dec._handle._h, ws, n, n_steps, self.L, C.c_void_p(out.data_ptr()),
-                                                        dec._stream()))
+        _lib.check(_lib.load().vit_hip_export_decisions(dec._handle._h, ws, n, n_steps, self.L, _ptr(out), dec._stream()))
         return f0.value, out
 
     def set_timing(self, enable: bool):

@@ -1,0 +1,162 @@
+"""The chunked receivers on top of BatchDecoder.decode_streams: push() symbols as they arrive, get decoded bytes back.
+
+`MultiStreamDecoder` serves n lockstep streams and holds everything there is to a receiver: the hold-back rule, the log of internal
+calls, the sub-byte carry, the running channel error totals and the first / done state.  `StreamDecoder` is its n_streams = 1 face
+(vit_hip_decode_streams with one stream launches exactly what vit_hip_decode_stream launches).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .decoder import BatchDecoder
+
+
+def _next_states(states, bits, K):
+    """decoder states [n] after the input bits [n][n_bits] (0/1) have been shifted in: bit j = the input bit j+1 steps back"""
+    states = np.asarray(states, dtype=np.int64).copy()
+    for j in range(max(bits.shape[1] - (K - 1), 0), bits.shape[1]):
+        states = (states << 1) | bits[:, j].astype(np.int64)
+    return states & ((1 << (K - 1)) - 1)
+
+
+class MultiStreamDecoder:
+    """A chunked receiver for n_streams lockstep streams: push() the same number of steps of each stream as they arrive, get one
+    `bytes` per stream back; finish() ends all streams (their last K-1 steps are the zero tail).
+
+    The pending symbols of all streams live in ONE device buffer [n_streams][pitch][R] whose pitch is rounded up to a multiple of
+    the window (and grown when a push needs it), so every internal call reads them in place on one shared window grid.
+
+    Every internal call is a segment of head + n*window + tail steps on the window grid (one uniform batch), BEGIN on the first.
+    What does not fill a window yet stays on the device: the last head + tail steps of the segment just decoded (the next one's
+    lead-in and this one's look-ahead) and at least one more window (window + K-1 steps), so that the final segment under END
+    always holds a full window -- with that, pushes of ANY sizes plus finish() decode, per stream, to exactly the bits of ONE
+    decode_stream call over that whole stream (tests/test_stream_cpu.py: chunked vs one call).  Whole bytes only: the sub-byte
+    remainder is carried to the next call; finish() pads the last byte with zeros.  `n_bits` counts the bits returned so far per
+    stream.
+
+    channel_errors=True: the object also keeps `.channel_errors`, two int64 arrays of length n_streams: the running (errors,
+    compared) of the re-encoded channel symbol error count (BatchDecoder.channel_errors) over every trellis step whose bit has been
+    emitted so far -- each step exactly once, however the pushes were cut; finish() adds the K-1 tail steps.  One more launch and
+    one small read-back per internal call for all streams; the last K-1 emitted bits are carried as the next call's start state.
+    Off (the default), nothing changes."""
+
+    # how the errors word it; StreamDecoder has its own
+    _RULE = "n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams"
+    _SHAPE, _FINISHED, _EMPTY = "[n_streams][steps][R]", "the streams are finished", "empty streams"
+
+    def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
+                 channel_errors: bool = False):
+        self.decoder = decoder
+        self.n_streams = int(n_streams)
+        self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
+        seg = self.head + self.window + self.tail
+        pitch = -(-seg // self.window) * self.window
+        if self.n_streams < 1 or decoder.streams_workspace_bytes(self.n_streams, pitch, seg, True, False, self.window, self.head,
+                                                                 self.tail) == 0:
+            raise ValueError(self._RULE)
+        self.n_bits = 0
+        self.calls = []                       # (steps, begin, end) of every internal call, for inspection
+        self._first = True
+        self._done = False
+        self._buf = None                      # device tensor [n_streams][pitch][R], pitch % window == 0
+        self._pending = 0                     # steps of it in use, per stream
+        self._carry = np.zeros((self.n_streams, 0), dtype=np.uint8)
+        self._totals = None                   # (errors, compared) per stream when they are kept
+        if channel_errors:
+            self._totals = (np.zeros(self.n_streams, dtype=np.int64), np.zeros(self.n_streams, dtype=np.int64))
+            self._state = np.zeros(self.n_streams, dtype=np.int64)    # the last K-1 emitted bits, as a decoder state
+
+    @property
+    def channel_errors(self):
+        if self._totals is None:
+            raise AttributeError("this receiver was made without channel_errors=True")
+        return self._totals
+
+    def _count(self, out, n_bits, end):
+        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted, from the segment's first emitted step on"""
+        dec = self.decoder
+        err, cmp = dec.channel_errors(self._buf[:, 0 if self._first else self.head:], out, n_bits, tail=end, start_state=self._state,
+                                      symbol_frame_stride=self._buf.shape[1] * dec.R)
+        self._totals = (self._totals[0] + err.cpu().numpy(), self._totals[1] + cmp.cpu().numpy())
+        self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits], dec.K)
+
+    def _append(self, symbols):
+        if symbols is None:
+            return
+        dec = self.decoder
+        if (symbols.dtype != dec._soft_dtype or not symbols.is_cuda or symbols.dim() < 2 or symbols.shape[0] != self.n_streams
+                or symbols[0].numel() % dec.R != 0):
+            raise ValueError(f"symbols must be a {dec._soft_dtype} CUDA tensor of {self._SHAPE}")
+        symbols = symbols.reshape(self.n_streams, -1, dec.R)
+        P, n = self._pending, symbols.shape[1]
+        if self._buf is None or P + n > self._buf.shape[1]:
+            # room for what is held back between calls as well, so that a steady flow of pushes of this size does not grow it again
+            pitch = -(-(P + n + self.head + 2 * self.window + self.tail) // self.window) * self.window
+            buf = dec.torch.empty((self.n_streams, pitch, dec.R), dtype=dec._soft_dtype, device=dec.device)
+            if P:
+                buf[:, :P] = self._buf[:, :P]
+            self._buf = buf
+        self._buf[:, P:P + n] = symbols
+        self._pending = P + n
+
+    def _decode(self, steps, end):
+        """one internal call over the first `steps` pending steps of every stream: the bytes it hands back, per stream"""
+        out, n_bits = self.decoder.decode_streams(self._buf, steps, self._first, end, self.window, self.head, self.tail)
+        self.calls.append((steps, self._first, end))
+        if self._totals is not None:
+            self._count(out, n_bits, end)
+        self._first = False
+        # whole bytes only: the rest waits in the carry, which the last call flushes
+        bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
+        keep = bits.shape[1] if end else bits.shape[1] - bits.shape[1] % 8
+        self._carry = bits[:, keep:]
+        self.n_bits += keep
+        return [np.packbits(row[:keep], bitorder="big").tobytes() for row in bits]
+
+    def push(self, symbols) -> list:
+        if self._done:
+            raise RuntimeError(self._FINISHED)
+        self._append(symbols)
+        P = self._pending
+        hold = self.head + self.window + self.decoder.K - 1
+        if P < hold + self.window:
+            return [b""] * self.n_streams
+        n = (P - hold) // self.window
+        data = self._decode(self.head + n * self.window + self.tail, False)
+        self._pending = P - n * self.window
+        self._buf[:, :self._pending] = self._buf[:, n * self.window:P].clone()
+        return data
+
+    def finish(self, symbols=None) -> list:
+        if self._done:
+            raise RuntimeError(self._FINISHED)
+        self._append(symbols)
+        if self._buf is None:
+            raise ValueError(self._EMPTY)
+        data = self._decode(self._pending, True)
+        self._done = True
+        self._buf = None
+        self._pending = 0
+        return data
+
+
+class StreamDecoder(MultiStreamDecoder):
+    """MultiStreamDecoder for ONE long stream: push() and finish() take any tensor of whole trellis steps ([steps][R], flat, or a view
+    that is not contiguous) and return `bytes`; `.channel_errors` (with channel_errors=True) is a pair of ints."""
+
+    _RULE = "window, head, tail outside the argument rule of vit_hip_decode_stream"
+    _SHAPE, _FINISHED, _EMPTY = "[steps][R]", "the stream is finished", "an empty stream"
+
+    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False):
+        super().__init__(decoder, 1, window, head, tail, channel_errors)
+
+    @property
+    def channel_errors(self):
+        errors, compared = super().channel_errors
+        return int(errors[0]), int(compared[0])
+
+    def push(self, symbols) -> bytes:
+        return super().push(None if symbols is None else symbols[None])[0]
+
+    def finish(self, symbols=None) -> bytes:
+        return super().finish(None if symbols is None else symbols[None])[0]
