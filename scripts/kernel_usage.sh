@@ -1,5 +1,5 @@
 #!/bin/bash
-# scripts/kernel_usage.sh <reg id | vit | vit_host | vit_tools> -- VGPRs / scratch / occupancy of every kernel of one translation unit
+# scripts/kernel_usage.sh <reg id | vit | vit_windows | vit_host | vit_tools | vit_encode> -- VGPRs / scratch / occupancy of every kernel of one translation unit
 cd "$(dirname "$0")/../viterbidecodercpp_amd/csrc"
 case "$1" in vit) SRC=vit_hip.hip; DEF="";; vit_*) SRC=$1.hip; DEF="";; *) SRC=reg_inst.hip; DEF="-DVIT_REG_ID=$1";; esac
 hipcc -O3 -std=c++17 --offload-arch=gfx950 $DEF -S --cuda-device-only -Rpass-analysis=kernel-resource-usage -o /dev/null $SRC 2>&1 |

@@ -11,10 +11,9 @@
 // rows between one stream's last window and the next one's first (the bridge windows, which straddle two segments) are initialised
 // like any other and never read by the stitch.  One stream is the case n_streams = 1.
 // Both are memory-bound and make one pass over their data; neither is specialised on the polynomials.  Included only from
-// vit_hip.hip (not from the register-plan units, whose kernel sources key the precompiled and run-time compiled caches).
+// vit_windows.hip (not from the register-plan units, whose kernel sources key the precompiled and run-time compiled caches).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "kernels_tb.hpp"
 
 namespace vit {
 
@@ -177,13 +176,8 @@ __global__ void __launch_bounds__(256) stream_stitch_kernel(StreamStitchArgs a) 
 
 // ---- launchers (hipGetLastError() after each: 0 / -1) -----------------------------------------------------------------------
 
-inline unsigned stream_blocks(uint64_t threads, uint64_t cap) {
-    const uint64_t b = (threads + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
-}
-
 inline int stream_launch_init(int error_bytes, const StreamInitArgs& a, hipStream_t st) {
-    const unsigned blocks = stream_blocks(a.total_chunks, 8192);      // memory-bound: grid-stride past 8192 blocks
+    const unsigned blocks = tb_blocks(a.total_chunks, 8192);          // memory-bound: grid-stride past 8192 blocks
     if (error_bytes == 2) hipLaunchKernelGGL(stream_init_kernel<uint16_t>, dim3(blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(stream_init_kernel<uint8_t>, dim3(blocks), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -191,7 +185,7 @@ inline int stream_launch_init(int error_bytes, const StreamInitArgs& a, hipStrea
 
 inline int stream_launch_stitch(const StreamStitchArgs& a, hipStream_t st) {
     const unsigned ny = a.n_streams < 65535u ? a.n_streams : 65535u;
-    hipLaunchKernelGGL(stream_stitch_kernel, dim3(stream_blocks(a.chunks, 0xFFFFFFFFull), ny), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(stream_stitch_kernel, dim3(tb_blocks(a.chunks, 0xFFFFFFFFull), ny), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -6,7 +6,7 @@
 //   3. tb_window_kernel     decoded bytes = bits [head, head + L) of the chainback over the extension, and the flag that the
 //                           path enters and leaves the window in the same state.
 // All three are memory- or latency-bound and make one pass over their data.  They are not specialised on the polynomials: one
-// instantiation per soft / error width.  Included only from vit_hip.hip (not from the register-plan units, whose kernel
+// instantiation per soft / error width.  Included only from vit_windows.hip (not from the register-plan units, whose kernel
 // sources key the precompiled and run-time compiled caches).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -215,6 +215,7 @@ __global__ void __launch_bounds__(256) tb_window_kernel(TbWindowArgs a) {
 
 // ---- launchers (hipGetLastError() after each: 0 / -1) -----------------------------------------------------------------------
 
+// workgroups of 256 for `threads` threads, at least one and at most `cap` (kernels_stream.hpp uses it too)
 inline unsigned tb_blocks(uint64_t threads, uint64_t cap) {
     const uint64_t b = (threads + 255) / 256;
     return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);

@@ -1,14 +1,12 @@
 // vit_hip.hip -- C ABI (include/vit_hip.h) over the gfx950 kernels: the decoder handle, plan selection, workspace layout and the
 // batched entry points.  Host-side logic only: argument checking and launches.  There is no CPU decode path in this library:
 // without a usable GPU every entry point fails with VIT_HIP_ERR_NO_DEVICE / VIT_HIP_ERR_RUNTIME.  The other routes of the ABI
-// live in vit_pipeline.hip, vit_host.hip and vit_tools.hip (vit_internal.hpp says what they share).
+// live in vit_windows.hip, vit_pipeline.hip, vit_host.hip, vit_tools.hip and vit_encode.hip (vit_internal.hpp says what they share).
 #include <stdio.h>
 
 #include "vit_internal.hpp"
 #include "kernels_lds.hpp"
 #include "kernels_lds2.hpp"
-#include "kernels_tb.hpp"
-#include "kernels_stream.hpp"
 #include "reg_jit.hpp"
 
 using namespace vit;
@@ -578,334 +576,6 @@ int vit_hip_reset_batch(vit_hip_handle h, size_t frames, const uint32_t* d_start
                            frames, (uint32_t)h->N, h->cfg_raw[1], h->cfg_raw[2]);
     VIT_HIP_CHECK(hipGetLastError());
     return VIT_HIP_OK;
-}
-
-namespace {
-// the caller-owned workspace of one tail-biting call, every sub-buffer 256-byte aligned (include/vit_hip.h)
-struct TbLayout {
-    size_t S_ext = 0, L_ext = 0, nbe = 0;          // extended steps, extended chainback bits, its bytes per frame
-    size_t dec = 0, ext = 0, met = 0, end = 0, bytes = 0, total = 0;   // offsets, and the whole size
-};
-
-// argument rule of the tail-biting entry points: L >= K, head and tail >= K-1, and sizes the launchers' 32-bit counters hold
-const char* tb_invalid(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail) {
-    const size_t K = (size_t)h->K;
-    if (L < K) return "tail-biting frames need L >= K";
-    if (head < K - 1 || tail < K - 1) return "head and tail must be >= K-1";
-    if (frames > 0x7FFFFFF0u || L > 0x10000000u || head > 0x10000000u || tail > 0x10000000u) return "batch too large";
-    return nullptr;
-}
-
-void tb_layout(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail, TbLayout& o) {
-    o.S_ext = head + L + tail;
-    o.L_ext = o.S_ext - ((size_t)h->K - 1);
-    o.nbe = (o.L_ext + 7) / 8;
-    o.dec = 0;
-    o.ext = align_up(vit_hip_workspace_bytes(h, frames, o.L_ext), 256);
-    o.met = o.ext + align_up(frames * o.S_ext * (size_t)h->R * (size_t)h->soft_bytes, 256);
-    o.end = o.met + align_up(frames * (size_t)h->N * (size_t)h->error_bytes, 256);
-    o.bytes = o.end + align_up(frames * sizeof(uint32_t), 256);
-    o.total = o.bytes + align_up(frames * o.nbe, 256);
-}
-}  // namespace
-
-size_t vit_hip_tail_biting_workspace_bytes(vit_hip_handle h, size_t frames, size_t L, size_t head, size_t tail) {
-    if (!h || tb_invalid(h, frames, L, head, tail)) return 0;
-    TbLayout lay;
-    tb_layout(h, frames, L, head, tail, lay);
-    return lay.total;
-}
-
-int vit_hip_decode_tail_biting_batch(vit_hip_handle h, const void* d_symbols, size_t frames, size_t L, size_t head, size_t tail,
-                                     void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, uint32_t* d_end_state_out,
-                                     uint8_t* d_tail_biting_ok, vit_hip_stream_t stream) {
-    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
-    if (const char* why = tb_invalid(h, frames, L, head, tail)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
-    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
-    TbLayout lay;
-    tb_layout(h, frames, L, head, tail, lay);
-    if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    if (frames == 0) return VIT_HIP_OK;
-    VIT_HIP_ON_DEVICE(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    void* ext = ws + lay.ext;
-    void* met = ws + lay.met;
-    uint32_t* end = (uint32_t*)(ws + lay.end);
-    uint8_t* ext_bytes = ws + lay.bytes;
-
-    // 1. the extended symbols and every state a start state
-    vit::TbGatherArgs g{};
-    g.symbols = d_symbols;
-    g.ext = ext;
-    g.metrics = met;
-    g.ext_elems = (uint64_t)frames * lay.S_ext * (uint64_t)h->R;
-    g.gather_chunks = (g.ext_elems * (uint64_t)h->soft_bytes + 15) / 16;
-    g.metric_bytes = (uint64_t)frames * (uint64_t)h->N * (uint64_t)h->error_bytes;
-    g.total_chunks = g.gather_chunks + (g.metric_bytes + 15) / 16;
-    g.L = (uint32_t)L; g.R = (uint32_t)h->R; g.S_ext = (uint32_t)lay.S_ext;
-    g.shift = (uint32_t)((L - head % L) % L);
-    const uint32_t start = h->cfg_raw[1];
-    g.fill = h->error_bytes == 2 ? (start & 0xFFFFu) * 0x00010001u : (start & 0xFFu) * 0x01010101u;
-    if (vit::tb_launch_gather(h->soft_bytes, g, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting gather launch failed");
-
-    // 2. the plan's own update over the whole extension, resumed in place from those metrics (every plan resumes: PLAN_LDS in place)
-    int rc = update_batch_impl(h, ext, 0, frames, 0, lay.S_ext, lay.L_ext, ws, lay.ext, met, met, nullptr, nullptr, stream);
-    if (rc != VIT_HIP_OK) return rc;
-
-    // 3. end state = smallest final metric
-    vit::TbSelectArgs s{};
-    s.metrics = met;
-    s.end_ws = end;
-    s.end_out = d_end_state_out;
-    s.frames = (uint32_t)frames;
-    s.log2N = (uint32_t)(h->K - 1);
-    if (vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting end-state launch failed");
-
-    // 4. the plan's own chainback over the extension from those states
-    rc = chainback_batch_impl(h, ws, frames, lay.L_ext, ext_bytes, end, stream, 0);
-    if (rc != VIT_HIP_OK) return rc;
-
-    // 5. the window [head, head + L) and the tail-biting flag
-    vit::TbWindowArgs w{};
-    w.ext_bytes = ext_bytes;
-    w.out = d_bytes_out;
-    w.ok = d_tail_biting_ok;
-    w.nbe = (uint32_t)lay.nbe;
-    w.nb = (uint32_t)((L + 7) / 8);
-    w.total = (uint64_t)frames * w.nb;
-    w.L = (uint32_t)L; w.head = (uint32_t)head; w.K = (uint32_t)h->K;
-    if (vit::tb_launch_window(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "tail-biting window launch failed");
-    return VIT_HIP_OK;
-}
-
-namespace {
-// the windows of one vit_hip_decode_stream / vit_hip_decode_streams call and its caller-owned workspace, every part 256-byte aligned
-// (include/vit_hip.h).  One stream is n_streams = 1: rows_u = n_u and one remainder frame, what vit_hip_decode_stream always laid out.
-struct StreamLayout {
-    size_t a = 0, b = 0, n = 0, n_u = 0;           // per stream: emitted range [a, b), windows, of which uniform (n_u == n or n - 1)
-    size_t S_u = 0, L_u = 0, nbe_u = 0;            // a uniform window's steps, chainback bits, bytes
-    size_t S_r = 0, L_r = 0, nbe_r = 0;            // the remainder window's (0 when every window has the same length)
-    size_t n_streams = 1, period = 0;              // streams; grid windows from one stream's window 0 to the next one's (pitch / W)
-    size_t rows_u = 0, rows_r = 0;                 // launched grid windows (n_streams - 1) * period + n_u; remainder frames
-    size_t dec_u = 0, dec_r = 0, met_u = 0, met_r = 0, end_u = 0, end_r = 0, bytes_u = 0, bytes_r = 0, total = 0;
-};
-
-// argument rule of the stream entry points; fills the window bookkeeping of `o` when the arguments pass
-const char* stream_invalid(vit_hip_handle h, size_t T, size_t W, size_t head, size_t tail, unsigned flags, StreamLayout& o) {
-    const size_t K = (size_t)h->K;
-    const bool begin = flags & VIT_HIP_STREAM_BEGIN, end = flags & VIT_HIP_STREAM_END;
-    if (flags & ~(unsigned)(VIT_HIP_STREAM_BEGIN | VIT_HIP_STREAM_END)) return "unknown stream flags";
-    if (head < K - 1 || tail < K - 1) return "head and tail must be >= K-1";
-    if (W < 8 || W < head || W < tail) return "the window must be >= 8, >= head and >= tail";
-    if (T > 0x7FFFFFF0u || W > 0x10000000u) return "segment too large";
-    if (T < head + tail + (begin ? 0 : 1)) return "the segment must hold head + tail steps (and one more without BEGIN)";
-    o.a = begin ? 0 : head;
-    o.b = end ? T - (K - 1) : T - tail;
-    if (o.b <= o.a) return "the segment emits no bit";
-    // b > a >= 0 and T >= head + tail; b >= head: END: T - (K-1) >= head + tail - (K-1) >= head; else T - tail >= head
-    o.n = (o.b - head) / W;
-    if (o.n < 1) o.n = 1;
-    o.S_u = head + W + tail;
-    const size_t last = T - (o.n - 1) * W;          // steps of the last window
-    o.n_u = last == o.S_u ? o.n : o.n - 1;
-    o.S_r = o.n_u == o.n ? 0 : last;
-    // the register plan addresses a tile's symbols through 32-bit offsets with the sign bit kept free (reg_update): the last of a
-    // tile's (at most 128) overlapped windows ends (tile - 1) * W + S_u steps into it; the remainder window is one frame
-    const size_t step_bytes = (size_t)h->R * (size_t)h->soft_bytes;
-    if ((127 * W + o.S_u) * step_bytes + 65536 >= 0x7FFF0000ull || o.S_r * step_bytes + 65536 >= 0x7FFF0000ull)
-        return "window too large for the launchers' 32-bit symbol offsets";
-    o.n_streams = 1;
-    o.period = 0;
-    o.rows_u = o.n_u;
-    o.rows_r = o.S_r ? 1 : 0;
-    return nullptr;
-}
-
-// the same for n_streams lockstep streams `pitch` steps apart: each stream under the rule above, all of them on one grid of W steps
-const char* streams_invalid(vit_hip_handle h, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
-                            StreamLayout& o) {
-    if (const char* why = stream_invalid(h, T, W, head, tail, flags, o)) return why;
-    if (n_streams < 1 || n_streams > 0x7FFFFFF0u) return "n_streams must be >= 1 (and within the launchers' batch limit)";
-    if (pitch < T || pitch % W != 0) return "pitch must be >= T and a multiple of the window";
-    o.n_streams = n_streams;
-    o.period = pitch / W;                           // > n_u, >= n: the last window of a stream ends inside its pitch
-    // no useful window on the grid (every stream is one remainder window): the grid is not launched
-    o.rows_u = o.n_u ? (n_streams - 1) * o.period + o.n_u : 0;
-    o.rows_r = o.S_r ? n_streams : 0;
-    if (o.rows_u > 0x7FFFFFF0u) return "too many windows for one batch";
-    // the remainder windows are a batch at stride pitch: a register-plan tile of them spans tile * pitch steps (reg_update's bound)
-    const size_t tile = h->plan == VIT_HIP_PLAN_REG ? (size_t)h->reg_code.tile : 1;
-    if (o.rows_r > 1 && pitch * (size_t)h->R * (size_t)h->soft_bytes * tile + 65536 >= 0x7FFF0000ull)
-        return "pitch too large for the launchers' 32-bit symbol offsets";
-    return nullptr;
-}
-
-// fills the workspace layout of `o` and returns its size
-size_t stream_layout(vit_hip_handle h, StreamLayout& o) {
-    const size_t K1 = (size_t)h->K - 1, row = (size_t)h->N * (size_t)h->error_bytes;
-    o.L_u = o.S_u - K1;
-    o.nbe_u = (o.L_u + 7) / 8;
-    o.L_r = o.S_r ? o.S_r - K1 : 0;
-    o.nbe_r = (o.L_r + 7) / 8;
-    o.dec_u = 0;
-    o.dec_r = o.dec_u + (o.rows_u ? align_up(vit_hip_workspace_bytes(h, o.rows_u, o.L_u), 256) : 0);
-    o.met_u = o.dec_r + (o.rows_r ? align_up(vit_hip_workspace_bytes(h, o.rows_r, o.L_r), 256) : 0);
-    o.met_r = o.met_u + align_up(o.rows_u * row, 256);
-    o.end_u = o.met_r + align_up(o.rows_r * row, 256);
-    o.end_r = o.end_u + align_up(o.rows_u * sizeof(uint32_t), 256);
-    o.bytes_u = o.end_r + align_up(o.rows_r * sizeof(uint32_t), 256);
-    // 16 bytes of slack behind each: the stitch kernel's loads stay inside the rows, this keeps them off the next part anyway
-    o.bytes_r = o.bytes_u + align_up(o.rows_u * o.nbe_u + 16, 256);
-    return o.total = o.bytes_r + align_up(o.rows_r * o.nbe_r + 16, 256);
-}
-
-// the launches of both entry points, once the arguments have passed.  pitch and out_pitch: unused with one stream
-int decode_streams_launch(vit_hip_handle h, const StreamLayout& lay, const void* d_symbols, size_t pitch, size_t W, size_t head,
-                          unsigned flags, void* d_workspace, uint8_t* d_bytes_out, size_t out_pitch, vit_hip_stream_t stream) {
-    VIT_HIP_ON_DEVICE(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const bool begin = flags & VIT_HIP_STREAM_BEGIN, end = flags & VIT_HIP_STREAM_END;
-    const bool rem = lay.S_r != 0, many = lay.n_streams > 1;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    void* met_u = ws + lay.met_u;
-    void* met_r = ws + lay.met_r;
-    uint32_t* end_u = (uint32_t*)(ws + lay.end_u);
-    uint32_t* end_r = (uint32_t*)(ws + lay.end_r);
-    const size_t row = (size_t)h->N * (size_t)h->error_bytes, step = (size_t)h->R * (size_t)h->soft_bytes;
-
-    // 1. the start metrics of every window, and end state 0 for the last one of every stream under END
-    vit::StreamInitArgs in{};
-    in.met_u = met_u;
-    in.met_r = met_r;
-    if (end) {
-        in.end_zero = rem ? end_r : end_u + (lay.n_u - 1);
-        in.end_zero_count = (uint32_t)lay.n_streams;
-        in.end_zero_stride = (uint32_t)(rem ? 1 : lay.period);
-    }
-    in.bytes_u = lay.rows_u * row;
-    in.bytes_r = lay.rows_r * row;
-    in.chunks_u = (in.bytes_u + 15) / 16;
-    in.total_chunks = in.chunks_u + (in.bytes_r + 15) / 16;
-    in.row_bytes = (uint32_t)row;
-    in.row_shift = (uint32_t)(h->K - 1) + (h->error_bytes == 2 ? 1u : 0u);
-    const uint32_t start = h->cfg_raw[1], non_start = h->cfg_raw[2];
-    in.fill = h->error_bytes == 2 ? (start & 0xFFFFu) * 0x00010001u : (start & 0xFFu) * 0x01010101u;
-    in.non_start = h->error_bytes == 2 ? (non_start & 0xFFFFu) * 0x00010001u : (non_start & 0xFFu) * 0x01010101u;
-    // window 0 of a stream is row s * period of the grid; with one stream row 0 alone (a period no other row reaches)
-    in.begin_period_u = !begin || !lay.rows_u ? 0u : (uint32_t)(many ? lay.period : lay.rows_u);
-    in.begin_r = begin && !lay.n_u ? 1u : 0u;
-    if (vit::stream_launch_init(h->error_bytes, in, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream init launch failed");
-
-    // 2. the plan's own update, resumed in place from those metrics: the grid windows as one batch whose frame stride is W steps of
-    //    the caller's buffer (the windows overlap; nothing is gathered), then the longer last windows as a batch of one frame per
-    //    stream at stride pitch
-    int rc;
-    if (lay.rows_u) {
-        rc = update_batch_impl(h, d_symbols, W * (size_t)h->R, lay.rows_u, 0, lay.S_u, lay.L_u, ws + lay.dec_u, lay.dec_r - lay.dec_u, met_u,
-                               met_u, nullptr, nullptr, stream, true);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-    if (rem) {
-        rc = update_batch_impl(h, (const uint8_t*)d_symbols + (lay.n - 1) * W * step, many ? pitch * (size_t)h->R : 0, lay.rows_r, 0, lay.S_r,
-                               lay.L_r, ws + lay.dec_r, lay.met_u - lay.dec_r, met_r, met_r, nullptr, nullptr, stream);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-
-    // 3. end state = smallest final metric, for every window but the last one of a stream under END
-    vit::TbSelectArgs s{};
-    s.log2N = (uint32_t)(h->K - 1);
-    s.metrics = met_u;
-    s.end_ws = end_u;
-    s.frames = (uint32_t)(lay.rows_u - (end && !rem && lay.rows_u ? 1 : 0));
-    if (end && !rem && many) {
-        s.keep_period = (uint32_t)lay.period;
-        s.keep_phase = (uint32_t)(lay.n_u - 1);
-    }
-    if (s.frames && vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
-    if (rem && !end) {
-        s.metrics = met_r;
-        s.end_ws = end_r;
-        s.frames = (uint32_t)lay.rows_r;
-        s.keep_period = 0;
-        if (vit::tb_launch_select(h->error_bytes, s, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream end-state launch failed");
-    }
-
-    // 4. the plan's own chainback of every window over all its steps, from those states
-    if (lay.rows_u) {
-        rc = chainback_batch_impl(h, ws + lay.dec_u, lay.rows_u, lay.L_u, ws + lay.bytes_u, end_u, stream, 0);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-    if (rem) {
-        rc = chainback_batch_impl(h, ws + lay.dec_r, lay.rows_r, lay.L_r, ws + lay.bytes_r, end_r, stream, 0);
-        if (rc != VIT_HIP_OK) return rc;
-    }
-
-    // 5. each window's share of the output, as one bit stream per stream; the bridge windows' rows are not read
-    vit::StreamStitchArgs w{};
-    w.rows_u = ws + lay.bytes_u;
-    w.row_r = ws + lay.bytes_r;
-    w.out = d_bytes_out;
-    w.out_pitch = many ? out_pitch : 0;
-    w.n_streams = (uint32_t)lay.n_streams;
-    w.period = (uint32_t)lay.period;
-    w.nb = (lay.b - lay.a + 7) / 8;
-    w.chunks = (w.nb + 15) / 16;
-    w.a = (uint32_t)lay.a; w.b = (uint32_t)lay.b;
-    w.n = (uint32_t)lay.n; w.n_u = (uint32_t)lay.n_u;
-    w.W = (uint32_t)W; w.head = (uint32_t)head;
-    w.nbe_u = (uint32_t)lay.nbe_u; w.nbe_r = (uint32_t)lay.nbe_r;
-    w.out_aligned = ((uintptr_t)d_bytes_out & 15u) == 0 && (w.out_pitch & 15u) == 0 ? 1u : 0u;
-    if (vit::stream_launch_stitch(w, st) != 0) return fail(VIT_HIP_ERR_RUNTIME, "stream stitch launch failed");
-    return VIT_HIP_OK;
-}
-
-// what both decode entry points do once their argument rule has passed: pointer, layout and workspace checks, the launches, n_bits_out
-int decode_streams_checked(vit_hip_handle h, StreamLayout& lay, const void* d_symbols, size_t pitch, size_t W, size_t head, unsigned flags,
-                           void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, size_t out_pitch, size_t* n_bits_out,
-                           vit_hip_stream_t stream) {
-    if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
-    if (workspace_bytes < stream_layout(h, lay)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    const int rc = decode_streams_launch(h, lay, d_symbols, pitch, W, head, flags, d_workspace, d_bytes_out, out_pitch, stream);
-    if (rc != VIT_HIP_OK) return rc;
-    if (n_bits_out) *n_bits_out = lay.b - lay.a;
-    return VIT_HIP_OK;
-}
-}  // namespace
-
-size_t vit_hip_stream_workspace_bytes(vit_hip_handle h, size_t T, size_t W, size_t head, size_t tail, unsigned flags) {
-    StreamLayout lay;
-    return !h || stream_invalid(h, T, W, head, tail, flags, lay) ? 0 : stream_layout(h, lay);
-}
-
-int vit_hip_decode_stream(vit_hip_handle h, const void* d_symbols, size_t T, size_t W, size_t head, size_t tail, unsigned flags,
-                          void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out, size_t* n_bits_out,
-                          vit_hip_stream_t stream) {
-    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
-    StreamLayout lay;
-    if (const char* why = stream_invalid(h, T, W, head, tail, flags, lay)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
-    return decode_streams_checked(h, lay, d_symbols, 0, W, head, flags, d_workspace, workspace_bytes, d_bytes_out, 0, n_bits_out, stream);
-}
-
-size_t vit_hip_streams_workspace_bytes(vit_hip_handle h, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head, size_t tail,
-                                       unsigned flags) {
-    StreamLayout lay;
-    return !h || streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay) ? 0 : stream_layout(h, lay);
-}
-
-int vit_hip_decode_streams(vit_hip_handle h, const void* d_symbols, size_t n_streams, size_t pitch, size_t T, size_t W, size_t head,
-                           size_t tail, unsigned flags, void* d_workspace, size_t workspace_bytes, uint8_t* d_bytes_out,
-                           size_t out_pitch_bytes, size_t* n_bits_out, vit_hip_stream_t stream) {
-    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
-    StreamLayout lay;
-    if (const char* why = streams_invalid(h, n_streams, pitch, T, W, head, tail, flags, lay)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
-    if (out_pitch_bytes < (lay.b - lay.a + 7) / 8) return fail(VIT_HIP_ERR_INVALID_ARG, "out_pitch_bytes shorter than ceil(n_out/8)");
-    return decode_streams_checked(h, lay, d_symbols, pitch, W, head, flags, d_workspace, workspace_bytes, d_bytes_out, out_pitch_bytes,
-                                  n_bits_out, stream);
 }
 
 static int vit_hip_get_kernel_resources_impl(vit_hip_handle h, int kernel, vit_hip_kernel_resources* out) {

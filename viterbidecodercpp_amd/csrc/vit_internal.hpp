@@ -1,8 +1,10 @@
 // vit_internal.hpp -- what the translation units of the C ABI share: the decoder handle, the error path, and the few entry points
 // one route calls in another.  Each kernel is launched from exactly ONE unit (there is no -fgpu-rdc: a kernel referenced from two
 // units would be emitted twice):
-//   vit_hip.hip      handle, plans, batched update / chainback / decode / export / depuncture / reset, tail-biting, one long stream
-//                    (kernels_lds.hpp, kernels_lds2.hpp, kernels_tb.hpp, kernels_stream.hpp; the register plan through reg_plan.hpp / reg_inst.hip)
+//   vit_hip.hip      handle, plans, batched update / chainback / decode / export / depuncture / reset
+//                    (kernels_lds.hpp, kernels_lds2.hpp; the register plan through reg_plan.hpp / reg_inst.hip)
+//   vit_windows.hip  tail-biting, one long stream, many lockstep streams: side passes around the plans' update / chainback, which it
+//                    calls as declared below (kernels_tb.hpp, kernels_stream.hpp)
 //   vit_pipeline.hip vit_hip_pipeline_* and its schedule rules (no kernel of its own)
 //   vit_host.hip     the single-decoder host route and the frame route (kernels_one.hpp)
 //   vit_tools.hip    synth, bit-error count, shader clock, kernel listing, precompile, RCCL table broadcast (kernels_synth.hpp)
