@@ -45,6 +45,9 @@
  *   vit_hip_encode_batch      ConvolutionalEncoder_ShiftRegister / _Lookup   include/viterbi/convolutional_encoder_shift_register.h:42-62,
  *                             convolutional_encoder_lookup.h, for a batch on the caller's bytes (start state, tail-biting, strides)
  *   vit_hip_channel_errors_batch  no reference counterpart: the re-encoded channel symbol error count (rule below)
+ *   vit_hip_sync_build / vit_hip_sync_search  no reference counterpart: node synchronisation -- the streams of a set of alignment
+ *                             hypotheses (symbol offset, puncture phase, I/Q rotation) from one received buffer, and their ranking by
+ *                             that count in one call (rule below), with vit_hip_sync_search_workspace_bytes
  *
  * Semantics are those of the reference SCALAR strategy (strict '>' decision, wrapping error_t arithmetic,
  * renormalise only when new_metric[0] >= threshold): SURVEY.md section 8(a').  All results are bit-exact.
@@ -523,6 +526,67 @@ int vit_hip_channel_errors_batch(vit_hip_handle h, const void* d_symbols, size_t
                                  size_t bytes_frame_stride, size_t frames, size_t L, unsigned flags,
                                  const uint32_t* d_start_state, uint32_t* d_errors, uint32_t* d_compared,
                                  vit_hip_stream_t stream);
+
+/* ---- node synchronisation: rank stream alignment hypotheses in one call ------------------------------------------------------
+ * A receiver that has just locked its demodulator does not know which received symbol is output 0 of a trellis step, where the
+ * puncturing period starts, or which of the BPSK / QPSK rotations the carrier loop settled in.  The standard answer (CCSDS / DVB-S
+ * node synchronisation) is to decode under every hypothesis and keep the one with the lowest re-encoded channel symbol error rate.
+ * A hypothesis is (offset, flags): `offset` = the number of received symbols in front of the first symbol of a puncturing period
+ * (one number for the symbol alignment within a step AND the puncture phase: callers enumerate 0 .. kept_per_period - 1,
+ * unpunctured kept_per_period = R); flags swap I and Q and negate either.  The four QPSK rotations are the flag sets
+ * {0, 1|2, 2|4, 1|4} up to the caller's I/Q convention, BPSK inversion is 2|4.
+ *
+ * The stream of a hypothesis, bit-exact.  d_received [n_received] soft_t; d_source_index [period_symbols] int32 with
+ * kept_per_period means what it means for vit_hip_depuncture_batch over ONE puncturing period (period_symbols a multiple of R;
+ * entries are < 0 or index the period's kept_per_period transmitted symbols); NULL / 0 / 0 is unpunctured (period_symbols =
+ * kept_per_period = R, the identity).  Output symbol k = t R + i, 0 <= k < T R:
+ *   p = k / period_symbols, s = source_index[k % period_symbols]; s < 0: the output is 0, the erasure vit_hip_depuncture_batch
+ *   inserts (an s >= kept_per_period reads as an erasure too); else j = offset + p kept_per_period + s, jj = j ^ 1 under SWAP_PAIRS
+ *   else j, v = received[jj], and if the negate flag for the parity of j (an index into the CALLER's buffer: even / odd are the
+ *   demodulator's I / Q) is set, v = clamp(high + low - v, soft_t's min, soft_t's max).  The output is v.
+ * The largest jj any hypothesis reads must be < n_received, else VIT_HIP_ERR_INVALID_ARG and nothing is launched.  The hypotheses
+ * are a HOST array, so the host checks this -- without reading the map, which lives on the device: with a map, a last, partial
+ * period (T R not a multiple of period_symbols) counts as if it read the period's last transmitted symbol.
+ *
+ * vit_hip_sync_build writes d_symbols_out [n_hyp][pitch][R] (pitch in steps, >= T; steps [T, pitch) are NOT written) in ONE launch.
+ * n_hyp <= 64: the hypotheses travel by value in the kernel arguments -- no host-to-device copy, nothing the caller must keep
+ * alive, and the call captures into a hipGraph.  n_hyp = 1 with pitch = T is how a receiver turns the hypothesis that won into the
+ * contiguous [T][R] stream vit_hip_decode_stream reads.  T R < 2^32.
+ *
+ * vit_hip_sync_search, by composition (T, W, head, tail and the workspace obey the rules of vit_hip_decode_streams unchanged):
+ *   1. build the hypothesis streams at pitch = W ceil(T / W) into the workspace;
+ *   2. vit_hip_decode_streams with flags = 0 (mid-stream): the emitted bits are steps [head, T - tail), n_out = T - head - tail
+ *      (segments of T = head + n W + tail keep it at five launches);
+ *   3. the encoder state in front of the first emitted step is unknown: with skip = 8 ceil((K-1)/8) the re-encoding starts at
+ *      emitted bit `skip`, bit j of its start state = emitted bit skip - 1 - j, 0 <= j < K-1 (the decoder's state numbering, as in
+ *      vit_hip_encode_batch).  n_out > skip is required;
+ *   4. vit_hip_channel_errors_batch with frames = n_hyp, no flags, the symbols from step head + skip at stride pitch R, the bytes from
+ *      byte skip / 8, L = n_out - skip and those start states: d_errors / d_compared [n_hyp] are its outputs;
+ *   5. d_best[0] (may be NULL) = the hypothesis no other beats: a beats b iff compared_a > 0 and (compared_b == 0 or
+ *      errors_a compared_b < errors_b compared_a, in 64-bit integers); on a tie the lower index wins.
+ * A TRANSPARENT code (every polynomial of odd weight: Voyager, IS-95A) decodes an inverted stream to inverted bits with the same
+ * count: 2|4 ties with 0 exactly when the symbols are symmetric about the midpoint, d_best names the lower index, and the inversion
+ * is resolved by the frame marker, not here.  For a type whose midpoint (high + low) / 2 is not 0 the inserted erasures (value 0)
+ * count as compared symbols, alike in every hypothesis.
+ * Errors: VIT_HIP_ERR_UNSUPPORTED when vit_hip_info.table_is_linear is 0 (search only); VIT_HIP_ERR_INVALID_ARG, with nothing
+ * launched and the outputs untouched, for n_hyp outside 1 .. 64, unknown flag bits, period_symbols % R != 0, kept_per_period outside
+ * 1 .. period_symbols, a read past n_received, n_out <= skip, a NULL buffer, and whatever vit_hip_decode_streams rejects;
+ * VIT_HIP_ERR_WORKSPACE for a workspace below vit_hip_sync_search_workspace_bytes (which returns 0 for arguments the call rejects)
+ * or not 256-byte aligned.
+ * Batch calls like the others: they only enqueue on `stream`, allocate nothing, synchronise nothing, can be captured into a
+ * hipGraph; several may be in flight on one handle, each with its own workspace. */
+typedef struct vit_hip_sync_hypothesis { uint32_t offset; uint32_t flags; } vit_hip_sync_hypothesis;
+#define VIT_HIP_SYNC_SWAP_PAIRS  1u   /* received symbols 2j and 2j+1 change places (I <-> Q) */
+#define VIT_HIP_SYNC_NEGATE_EVEN 2u   /* symbols at an even received index are mirrored about (high+low)/2 */
+#define VIT_HIP_SYNC_NEGATE_ODD  4u   /* ... at an odd received index */
+int vit_hip_sync_build(vit_hip_handle h, const void* d_received, size_t n_received, const int32_t* d_source_index,
+                       size_t period_symbols, size_t kept_per_period, const vit_hip_sync_hypothesis* hypotheses, size_t n_hyp,
+                       size_t T, size_t pitch, void* d_symbols_out, vit_hip_stream_t stream);
+size_t vit_hip_sync_search_workspace_bytes(vit_hip_handle h, size_t n_hyp, size_t T, size_t W, size_t head, size_t tail);
+int vit_hip_sync_search(vit_hip_handle h, const void* d_received, size_t n_received, const int32_t* d_source_index,
+                        size_t period_symbols, size_t kept_per_period, const vit_hip_sync_hypothesis* hypotheses, size_t n_hyp,
+                        size_t T, size_t W, size_t head, size_t tail, void* d_workspace, size_t workspace_bytes, uint32_t* d_errors,
+                        uint32_t* d_compared, uint32_t* d_best, vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

@@ -142,6 +142,28 @@ public:
         check(vit_hip_channel_errors_batch(m_hip, d_symbols, symbol_frame_stride, d_bytes, bytes_frame_stride, frames, total_bits,
                                            flags, d_start_state, d_errors, d_compared, stream), "vit_hip_channel_errors_batch");
     }
+    // node synchronisation (vit_hip_sync_build / vit_hip_sync_search): the [steps][R] streams of up to 64 alignment hypotheses (a HOST
+    // array of {offset, VIT_HIP_SYNC_* flags}) from one received buffer -- d_source_index / period_symbols / kept_per_period describe
+    // ONE puncturing period as for depuncture(), nullptr / 0 / 0 = unpunctured -- and their ranking by the re-encoded channel symbol
+    // error count in one call: d_errors / d_compared [n_hyp] and d_best [1] (may be nullptr) are the results.  window / head / tail as
+    // decode_streams (0: the defaults); pitch in steps (0: `steps`).  The workspace is caller-owned.
+    void sync_build(const soft_t* d_received, size_t n_received, const int32_t* d_source_index, size_t period_symbols,
+                    size_t kept_per_period, const vit_hip_sync_hypothesis* hypotheses, size_t n_hyp, size_t steps,
+                    soft_t* d_symbols_out, size_t pitch = 0, void* stream = nullptr) {
+        check(vit_hip_sync_build(m_hip, d_received, n_received, d_source_index, period_symbols, kept_per_period, hypotheses, n_hyp, steps,
+                                 pitch ? pitch : steps, d_symbols_out, stream), "vit_hip_sync_build");
+    }
+    size_t sync_search_workspace_bytes(size_t n_hyp, size_t steps, size_t window = 0, size_t head = 0, size_t tail = 0) const {
+        return vit_hip_sync_search_workspace_bytes(m_hip, n_hyp, steps, window_or_default(window), extension(head), extension(tail));
+    }
+    void sync_search(const soft_t* d_received, size_t n_received, const int32_t* d_source_index, size_t period_symbols,
+                     size_t kept_per_period, const vit_hip_sync_hypothesis* hypotheses, size_t n_hyp, size_t steps, void* d_workspace,
+                     size_t workspace_size, uint32_t* d_errors, uint32_t* d_compared, uint32_t* d_best = nullptr, size_t window = 0,
+                     size_t head = 0, size_t tail = 0, void* stream = nullptr) {
+        check(vit_hip_sync_search(m_hip, d_received, n_received, d_source_index, period_symbols, kept_per_period, hypotheses, n_hyp, steps,
+                                  window_or_default(window), extension(head), extension(tail), d_workspace, workspace_size, d_errors,
+                                  d_compared, d_best, stream), "vit_hip_sync_search");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

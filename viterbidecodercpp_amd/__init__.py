@@ -7,7 +7,8 @@ from .codes import COMMON_CODES, Code, DecoderConfig, get_decoding_config, SOFT1
 from .decoder import (BatchDecoder, DecodePipeline, ViterbiBranchTable, ViterbiDecoder_Config, ViterbiDecoder_Core,  # noqa: F401
                       ViterbiDecoder_HIP, pack_blob)
 from .stream import MultiStreamDecoder, StreamDecoder  # noqa: F401
-from . import _lib, dist, synth  # noqa: F401
+from .sync import enumerate_hypotheses  # noqa: F401
+from . import _lib, dist, sync, synth  # noqa: F401
 
 __all__ = ["COMMON_CODES", "Code", "DecoderConfig", "get_decoding_config", "SOFT16", "SOFT8", "HARD8", "BatchDecoder", "DecodePipeline",
-           "MultiStreamDecoder", "StreamDecoder", "ViterbiBranchTable", "ViterbiDecoder_Config", "ViterbiDecoder_Core", "ViterbiDecoder_HIP", "pack_blob"]
+           "MultiStreamDecoder", "StreamDecoder", "ViterbiBranchTable", "ViterbiDecoder_Config", "ViterbiDecoder_Core", "ViterbiDecoder_HIP", "enumerate_hypotheses", "pack_blob"]

@@ -33,6 +33,7 @@ EXPORTS = [
     "vit_hip_stream_workspace_bytes", "vit_hip_decode_stream",
     "vit_hip_streams_workspace_bytes", "vit_hip_decode_streams",
     "vit_hip_encode_batch", "vit_hip_channel_errors_batch",
+    "vit_hip_sync_build", "vit_hip_sync_search_workspace_bytes", "vit_hip_sync_search",
 ]
 
 
@@ -70,6 +71,13 @@ class VitHipKernelResources(C.Structure):
 KERNEL_UPDATE, KERNEL_CHAINBACK, KERNEL_CHAINBACK_ALT, KERNEL_RESUME = 0, 1, 2, 3
 STREAM_BEGIN, STREAM_END = 1, 2
 ENCODE_TAIL, ENCODE_TAIL_BITING = 1, 2
+SYNC_SWAP_PAIRS, SYNC_NEGATE_EVEN, SYNC_NEGATE_ODD = 1, 2, 4
+SYNC_MAX_HYPOTHESES = 64
+
+
+class VitHipSyncHypothesis(C.Structure):
+    """vit_hip_sync_hypothesis: received symbols in front of a puncturing period, and the SYNC_* flags"""
+    _fields_ = [("offset", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class VitHipError(RuntimeError):
@@ -133,6 +141,10 @@ def load():
     L.vit_hip_decode_streams.argtypes = [vp, vp, sz, sz, sz, sz, sz, sz, C.c_uint, vp, sz, vp, sz, C.POINTER(sz), vp]
     L.vit_hip_encode_batch.argtypes = [vp, vp, sz, sz, sz, C.c_uint, vp, vp, sz, vp, vp]
     L.vit_hip_channel_errors_batch.argtypes = [vp, vp, sz, vp, sz, sz, sz, C.c_uint, vp, vp, vp, vp]
+    L.vit_hip_sync_build.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(VitHipSyncHypothesis), sz, sz, sz, vp, vp]
+    L.vit_hip_sync_search_workspace_bytes.restype = sz
+    L.vit_hip_sync_search_workspace_bytes.argtypes = [vp, sz, sz, sz, sz, sz]
+    L.vit_hip_sync_search.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(VitHipSyncHypothesis), sz, sz, sz, sz, sz, vp, sz, vp, vp, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -53,6 +53,33 @@ int enc_prepare(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_str
 
 }  // namespace
 
+// vit_hip_channel_errors_batch, and the same count into counters the caller has zeroed on `stream` itself (zero_counters = false)
+int vit::channel_errors_impl(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_stride, const uint8_t* d_bytes,
+                             size_t bytes_frame_stride, size_t frames, size_t L, unsigned flags, const uint32_t* d_start_state,
+                             uint32_t* d_errors, uint32_t* d_compared, bool zero_counters, vit_hip_stream_t stream) {
+    EncArgs a;
+    unsigned blocks = 0;
+    if (h && frames != 0 && !d_errors) return fail(VIT_HIP_ERR_INVALID_ARG, "d_errors is NULL");
+    const int pre = enc_prepare(h, d_symbols, symbol_frame_stride, d_bytes, bytes_frame_stride, frames, L, flags, d_start_state, 8, a, blocks);
+    if (pre != 0) return pre < 0 ? pre : VIT_HIP_OK;
+    a.symbols = const_cast<void*>(d_symbols);
+    a.errors = d_errors;
+    a.compared = d_compared;
+    VIT_HIP_ON_DEVICE(h->device);
+    // the call overwrites its outputs: the kernel adds into zeroed counters
+    if (zero_counters) {
+        VIT_HIP_CHECK(hipMemsetAsync(d_errors, 0, frames * sizeof(uint32_t), (hipStream_t)stream));
+        if (d_compared) VIT_HIP_CHECK(hipMemsetAsync(d_compared, 0, frames * sizeof(uint32_t), (hipStream_t)stream));
+    }
+    const int rc = with_rate(h->R, -1, [&](auto r) {
+        if (h->soft_bytes == 2) hipLaunchKernelGGL((channel_errors_kernel<int16_t, r()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((channel_errors_kernel<int8_t, r()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
+    if (rc != 0) return fail(VIT_HIP_ERR_RUNTIME, "channel error kernel launch failed");
+    return VIT_HIP_OK;
+}
+
 extern "C" {
 
 int vit_hip_encode_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_frame_stride, size_t frames, size_t L, unsigned flags,
@@ -77,25 +104,8 @@ int vit_hip_encode_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_
 int vit_hip_channel_errors_batch(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_stride, const uint8_t* d_bytes,
                                  size_t bytes_frame_stride, size_t frames, size_t L, unsigned flags, const uint32_t* d_start_state,
                                  uint32_t* d_errors, uint32_t* d_compared, vit_hip_stream_t stream) {
-    EncArgs a;
-    unsigned blocks = 0;
-    if (h && frames != 0 && !d_errors) return fail(VIT_HIP_ERR_INVALID_ARG, "d_errors is NULL");
-    const int pre = enc_prepare(h, d_symbols, symbol_frame_stride, d_bytes, bytes_frame_stride, frames, L, flags, d_start_state, 8, a, blocks);
-    if (pre != 0) return pre < 0 ? pre : VIT_HIP_OK;
-    a.symbols = const_cast<void*>(d_symbols);
-    a.errors = d_errors;
-    a.compared = d_compared;
-    VIT_HIP_ON_DEVICE(h->device);
-    // the call overwrites its outputs: the kernel adds into zeroed counters
-    VIT_HIP_CHECK(hipMemsetAsync(d_errors, 0, frames * sizeof(uint32_t), (hipStream_t)stream));
-    if (d_compared) VIT_HIP_CHECK(hipMemsetAsync(d_compared, 0, frames * sizeof(uint32_t), (hipStream_t)stream));
-    const int rc = with_rate(h->R, -1, [&](auto r) {
-        if (h->soft_bytes == 2) hipLaunchKernelGGL((channel_errors_kernel<int16_t, r()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((channel_errors_kernel<int8_t, r()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    });
-    if (rc != 0) return fail(VIT_HIP_ERR_RUNTIME, "channel error kernel launch failed");
-    return VIT_HIP_OK;
+    return channel_errors_impl(h, d_symbols, symbol_frame_stride, d_bytes, bytes_frame_stride, frames, L, flags, d_start_state, d_errors,
+                               d_compared, true, stream);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@
 //   vit_host.hip     the single-decoder host route and the frame route (kernels_one.hpp)
 //   vit_tools.hip    synth, bit-error count, shader clock, kernel listing, precompile, RCCL table broadcast (kernels_synth.hpp)
 //   vit_encode.hip   the encoder on the caller's bytes and the re-encoded channel symbol error count (kernels_enc.hpp)
+//   vit_sync.hip     node synchronisation: the streams of a set of alignment hypotheses and their ranking, around the C ABI's own
+//                    vit_hip_decode_streams and the body of vit_hip_channel_errors_batch, declared below (kernels_sync.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -140,6 +142,13 @@ int lds_chainback(vit_hip_handle h, const uint64_t* d_decisions, size_t frames, 
                   const uint32_t* d_end, hipStream_t st);
 // PLAN_LDS2: does the chainback kernel fit beside the update waves of this handle's code (kernels_lds2.hpp)?
 bool lds2_chainback_fits(vit_hip_handle h);
+
+// ---- defined in vit_encode.hip ----
+// the body of vit_hip_channel_errors_batch.  zero_counters = false: the kernel adds into d_errors / d_compared as they are -- a caller
+// that zeroes them in a kernel of its own on `stream` (the synchronisation search) enqueues no memset
+int channel_errors_impl(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_stride, const uint8_t* d_bytes,
+                        size_t bytes_frame_stride, size_t frames, size_t L, unsigned flags, const uint32_t* d_start_state,
+                        uint32_t* d_errors, uint32_t* d_compared, bool zero_counters, vit_hip_stream_t stream);
 
 }  // namespace vit
 

@@ -728,6 +728,74 @@ class BatchDecoder:
             self._stream()))
         return err, cmp
 
+    def _sync_args(self, received, hypotheses, mask):
+        """(hypothesis array, count, source map tensor or None, period_symbols, kept_per_period) of a sync_build / sync_search call"""
+        t = self.torch
+        if received.dtype != self._soft_dtype or not received.is_cuda or received.dim() != 1 or not received.is_contiguous():
+            raise ValueError(f"received must be a contiguous 1-D {self._soft_dtype} CUDA tensor")
+        hyps = [(int(o), int(f)) for o, f in hypotheses]
+        if not 1 <= len(hyps) <= _lib.SYNC_MAX_HYPOTHESES:
+            raise ValueError(f"1 to {_lib.SYNC_MAX_HYPOTHESES} hypotheses per call")
+        arr = (_lib.VitHipSyncHypothesis * len(hyps))(*hyps)
+        if mask is None:
+            return arr, len(hyps), None, 0, 0
+        mask = np.asarray(mask).astype(bool).reshape(-1)
+        if mask.size == 0 or mask.size % self.R != 0 or not mask.any():
+            raise ValueError("the puncturing mask must cover whole trellis steps (a multiple of R symbols) and keep a symbol")
+        key = mask.tobytes()
+        cached = getattr(self, "_sync_map", None)
+        if cached is None or cached[0] != key:             # the map is per puncturing scheme: build and upload it once
+            idx = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
+            cached = (key, t.from_numpy(idx).to(self.device))
+            self._sync_map = cached
+        return arr, len(hyps), cached[1], mask.size, int(mask.sum())
+
+    def sync_build(self, received, hypotheses, steps: int, mask=None, pitch: int = None, out=None):
+        """the [steps][R] stream of every alignment hypothesis from ONE received buffer (vit_hip_sync_build): hypotheses is a
+        sequence of (offset, flags) -- offset = received symbols in front of a puncturing period, flags of _lib.SYNC_SWAP_PAIRS /
+        SYNC_NEGATE_EVEN / SYNC_NEGATE_ODD (sync.enumerate_hypotheses makes the usual sets) --, mask the 0/1 puncturing mask over ONE
+        period as depuncture() takes it (None: unpunctured).  returns [n_hyp][pitch][R] (pitch in steps, default `steps`); the steps
+        behind `steps` are not written.  One hypothesis with the default pitch is what decode_stream / StreamDecoder.push read."""
+        t = self.torch
+        arr, n, d_idx, period, kept = self._sync_args(received, hypotheses, mask)
+        steps = int(steps)
+        pitch = steps if pitch is None else int(pitch)
+        if out is None:
+            out = t.empty((n, pitch, self.R), dtype=self._soft_dtype, device=self.device)
+        elif not self._is_symbols(out) or out.numel() != n * pitch * self.R:
+            raise ValueError(f"out must be a contiguous {self._soft_dtype} CUDA tensor of [{n}][{pitch}][{self.R}]")
+        _lib.check(_lib.load().vit_hip_sync_build(self._handle._h, _ptr(received), received.numel(), _ptr(d_idx), period, kept, arr, n,
+                                                  steps, pitch, _ptr(out), self._stream()))
+        return out
+
+    def sync_search_workspace_bytes(self, n_hyp: int, steps: int, window: int = None, head: int = None, tail: int = None) -> int:
+        window, head, tail, _ = self._stream_args(window, head, tail, False, False)
+        return _lib.load().vit_hip_sync_search_workspace_bytes(self._handle._h, int(n_hyp), int(steps), window, head, tail)
+
+    def sync_search(self, received, hypotheses, steps: int, mask=None, window: int = None, head: int = None, tail: int = None,
+                    workspace=None):
+        """node synchronisation in one call (vit_hip_sync_search): the streams of all hypotheses (as sync_build) are decoded as
+        mid-stream segments of `steps` steps (window / head / tail as decode_streams), re-encoded from the decoded bits and compared
+        with their own symbols.  returns (errors, compared, best): int32 CUDA tensors [n_hyp], [n_hyp] and [1] -- the re-encoded
+        channel symbol error count of every hypothesis and the index of the one with the lowest rate (the lower index on a tie:
+        on a transparent code an inverted stream ties with the upright one).  Nothing is copied to the host."""
+        t = self.torch
+        arr, n, d_idx, period, kept = self._sync_args(received, hypotheses, mask)
+        steps = int(steps)
+        window, head, tail, _ = self._stream_args(window, head, tail, False, False)
+        need = _lib.load().vit_hip_sync_search_workspace_bytes(self._handle._h, n, steps, window, head, tail)
+        if need == 0:
+            raise ValueError(f"a synchronisation search needs what decode_streams needs and more than 8*ceil((K-1)/8) emitted bits, on "
+                             f"a linear code (K = {self.K}, steps = {steps}, window = {window}, head = {head}, tail = {tail})")
+        ws = self._scratch(need, workspace)
+        err = t.empty(n, dtype=t.int32, device=self.device)
+        cmp = t.empty(n, dtype=t.int32, device=self.device)
+        best = t.empty(1, dtype=t.int32, device=self.device)
+        _lib.check(_lib.load().vit_hip_sync_search(
+            self._handle._h, _ptr(received), received.numel(), _ptr(d_idx), period, kept, arr, n, steps, window, head, tail, _ptr(ws),
+            ws.numel() * ws.element_size(), _ptr(err), _ptr(cmp), _ptr(best), self._stream()))
+        return err, cmp, best
+
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The
         workspace is an array of independent slabs of `workspace_tile_frames` frames (vit_hip_info), so `frames` frames
