@@ -89,3 +89,29 @@ def check_batch_against_oracle(oracle, code, decode_type, F, L, ebn0, seed, plan
         assert bad.size == 0, f"chainback bytes differ first at (frame, byte) = {bad[0]} of {len(bad)}"
     torch.cuda.synchronize()
     return dec
+
+
+def sync_search_raw(dec, case, workspace_ptr, workspace_bytes, errors, compared, best):
+    """vit_hip_sync_search of a case of tests/sync_reference.py (make_case) through the C ABI, with the caller's workspace (an
+    address) and outputs (int32 CUDA tensors or views of one); synchronises and returns the call's code"""
+    import ctypes as C
+
+    import torch
+
+    from viterbidecodercpp_amd import _lib
+    from tests import sync_reference as ref
+
+    lib = _lib.load()
+    ptr = lambda t: C.c_void_p(t.data_ptr())                                   # noqa: E731
+    d_rec = torch.from_numpy(case["received"]).cuda()
+    hyps = case["hypotheses"]
+    arr = (_lib.VitHipSyncHypothesis * len(hyps))(*hyps)
+    d_map, period, kept = None, 0, 0
+    if case["mask"] is not None:
+        idx, kept = ref.source_map(case["mask"])
+        d_map, period = torch.from_numpy(idx).cuda(), idx.size
+    rc = lib.vit_hip_sync_search(dec._handle._h, ptr(d_rec), d_rec.numel(), None if d_map is None else ptr(d_map), period, kept, arr,
+                                 len(hyps), case["T"], case["W"], case["head"], case["tail"], C.c_void_p(workspace_ptr), workspace_bytes,
+                                 ptr(errors), ptr(compared), ptr(best), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    return rc

@@ -2,7 +2,9 @@
 (widths, rates, masks, offsets, flag sets, the clamp, a pitch behind the steps, one and 64 hypotheses, a map too long for LDS), the
 counts and the winner of the search EQUAL to the reference's for the cases of tests/test_sync_cpu.py on the register plan, PLAN_LDS2
 and the forced PLAN_LDS, a longer last window, the call captured into a graph and replayed on a second buffer, every argument
-rejection with the outputs untouched, and the winning hypothesis fed to decode_stream."""
+rejection with the outputs untouched, and the winning hypothesis fed to decode_stream.  The int8 widths (the channel's noise on the
+midpoint under HARD8), a state of half a byte and one of 10 bits, 64 hypotheses, one, and extensions and windows that put the count's
+first symbol at every alignment enc_load tells apart run the same comparison."""
 import ctypes as C
 import functools
 
@@ -10,9 +12,10 @@ import numpy as np
 import pytest
 
 from viterbidecodercpp_amd import COMMON_CODES, BatchDecoder, _lib
+from viterbidecodercpp_amd.codes import Code
 from viterbidecodercpp_amd.sync import NEG_EVEN, NEG_ODD, SWAP
 from tests import sync_reference as ref
-from tests.helpers import DECODE_TYPES, make_table_config
+from tests.helpers import DECODE_TYPES, make_table_config, sync_search_raw
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +24,7 @@ CODE_OF_RATE = {2: ref.VOYAGER, 3: ref.LTE, 4: 4}
 
 @functools.lru_cache(maxsize=None)
 def decoder(code_id, decode_type, plan=_lib.PLAN_AUTO):
-    code = COMMON_CODES[code_id]
+    code = code_id if isinstance(code_id, Code) else COMMON_CODES[code_id]
     pc, table, config = make_table_config(code, decode_type)
     return code, pc, BatchDecoder(table, config, plan=plan)
 
@@ -101,20 +104,66 @@ def run_search(dec, c, received=None, **kw):
     return err.cpu().numpy().astype(np.int64), cmp.cpu().numpy().astype(np.int64), int(best.item())
 
 
-SEARCHES = [(name, _lib.PLAN_AUTO) for name in ref.CPU_CASES + ["voyager_long"]] + [("voyager", _lib.PLAN_LDS), ("voyager_3_4", _lib.PLAN_LDS)]
+SEARCHES = [(name, _lib.PLAN_LDS2 if name == "k11_lds2" else _lib.PLAN_AUTO) for name in ref.CPU_CASES + ["voyager_long"]] + [
+    ("voyager", _lib.PLAN_LDS), ("voyager_3_4", _lib.PLAN_LDS), ("voy_hard8", _lib.PLAN_LDS), ("lte_soft8", _lib.PLAN_LDS)]
 
 
 @pytest.mark.parametrize("name,plan", SEARCHES)
 def test_sync_search_equals_the_reference(oracle, name, plan):
     c = ref.make_case(name)
     want_err, want_cmp, want_best, _ = ref.case_reference(oracle, name)
-    code, pc, dec = decoder(COMMON_CODES.index(c["code"]), c["decode_type"], plan)
+    code, pc, dec = decoder(c["code"], c["decode_type"], plan)
     assert dec.plan == {("cassini", _lib.PLAN_AUTO): _lib.PLAN_LDS2}.get((name, plan), plan or _lib.PLAN_REG)
     err, cmp, best = run_search(dec, c)
     assert err.tolist() == want_err.tolist() and cmp.tolist() == want_cmp.tolist(), (err, want_err, cmp, want_cmp)
     assert best == want_best
+    if name == "voy_hard8":
+        assert len(set(cmp.tolist())) > 1, "the hypotheses were to compare different numbers of symbols"
     need = dec.sync_search_workspace_bytes(len(c["hypotheses"]), c["T"], c["W"], c["head"], c["tail"])
     assert need > 0 and need % 256 == 0
+
+
+@pytest.mark.parametrize("name", ["voyager_64", "voyager_64_reversed", "voyager_1"])
+def test_sync_search_hypothesis_counts(oracle, name):
+    """64 hypotheses (offsets 0 .. 7 under all 8 flag sets: every lane of the start-state and ranking kernels, 64 streams in the
+    decode, the largest workspace), the same list reversed (the winner in another lane) and the truth alone.  The outputs are three
+    slices of one poisoned buffer: what lies between and behind them is as it was"""
+    import torch
+    c = ref.make_case(name)
+    n = len(c["hypotheses"])
+    want_err, want_cmp, want_best, _ = ref.case_reference(oracle, name)
+    code, pc, dec = decoder(c["code"], c["decode_type"])
+    POISON = -7
+    buf = torch.full((256,), POISON, dtype=torch.int32, device="cuda")
+    e0, c0, b0 = 3, 3 + n + 13, 3 + n + 13 + n + 6                    # 3 in front, 13 and 6 between, the rest behind
+    need = dec.sync_search_workspace_bytes(n, c["T"], c["W"], c["head"], c["tail"])
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    assert sync_search_raw(dec, c, ws.data_ptr(), need, buf[e0:e0 + n], buf[c0:c0 + n], buf[b0:b0 + 1]) == _lib.OK
+    host = buf.cpu().numpy().astype(np.int64)
+    assert host[e0:e0 + n].tolist() == want_err.tolist() and host[c0:c0 + n].tolist() == want_cmp.tolist()
+    best = int(host[b0])
+    assert best == want_best and ref.aligned(c, c["hypotheses"][best])
+    if n == 1:
+        assert best == 0
+    written = np.zeros(host.size, dtype=bool)
+    written[e0:e0 + n] = written[c0:c0 + n] = written[b0] = True
+    assert written[:b0 + 1].sum() == 2 * n + 1 and (host[~written] == POISON).all(), np.flatnonzero((host != POISON) & ~written)
+    if name == "voyager_64_reversed":
+        assert best != ref.case_reference(oracle, "voyager_64")[2]
+
+
+@pytest.mark.parametrize("name,residue", ref.SHAPE_CASES)
+def test_sync_search_extensions_and_windows(oracle, name, residue):
+    """head != tail from {K-1, K, 2K+1, 8(K-1)}, W no multiple of head, a last window 1 or W - 1 steps longer: the count's first
+    symbol sits `residue` bytes into a row (ref.SHAPE_CASES lists them; tests/test_sync_cpu.py checks the list), rows at pitches that
+    are no multiple of 16 bytes.  Short extensions decode poorly -- the reference's decode is as poor, and the counts are equal"""
+    c = ref.make_case(name)
+    want_err, want_cmp, want_best, _ = ref.case_reference(oracle, name)
+    code, pc, dec = decoder(c["code"], c["decode_type"])
+    assert dec.plan == _lib.PLAN_REG
+    err, cmp, best = run_search(dec, c)
+    assert err.tolist() == want_err.tolist() and cmp.tolist() == want_cmp.tolist(), (residue, err, want_err, cmp, want_cmp)
+    assert best == want_best and ref.equivalent(code, c["hypotheses"][best], c["truth"])
 
 
 def test_sync_search_captured_into_a_graph(oracle):
@@ -230,7 +279,7 @@ def test_the_winning_hypothesis_decodes_to_the_data(name):
     """the winner, built alone at pitch = steps, is the stream decode_stream reads: its bits are the transmitted data (inverted when
     the channel inverted a transparent code and the tie went to the upright hypothesis)"""
     c = ref.make_case(name)
-    code, pc, dec = decoder(COMMON_CODES.index(c["code"]), c["decode_type"])
+    code, pc, dec = decoder(c["code"], c["decode_type"])
     err, cmp, best = run_search(dec, c)
     winner = c["hypotheses"][best]
     assert ref.equivalent(code, winner, c["truth"])

@@ -3,14 +3,17 @@ large as the *_workspace_bytes functions say and cut out of a larger poisoned bu
 bytes in front of and behind the workspace are untouched.  The shapes are the smallest at which a misplaced part of the layout
 shows: at K = 3 SOFT8 a metrics row is 4 bytes, so every part is mostly padding and a part that starts one slot early lands on its
 neighbour's data; with a remainder window both halves of the stream layout exist, without one (and with nothing but remainder
-windows, rows_u == 0) the conditional parts are empty."""
+windows, rows_u == 0) the conditional parts are empty.  The workspace of a synchronisation search (csrc/vit_sync.hip) carves the
+hypothesis streams, their decoded bytes and the start states in front of a decode_streams workspace: 64 hypotheses make it as large as
+it gets, an int8 search with rows of 300 bytes makes every part mostly padding."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from viterbidecodercpp_amd import COMMON_CODES, BatchDecoder, _lib
-from tests.helpers import make_table_config, oracle_cfg
+from tests import sync_reference
+from tests.helpers import make_table_config, oracle_cfg, sync_search_raw
 from tests.stream_reference import BEGIN, END, default_extension, make_stream, stream_reference
 from tests.tb_reference import tb_frames, tb_reference
 
@@ -94,3 +97,22 @@ def test_exact_workspace_between_guards(oracle, code, decode_type, route):
         assert n_bits.value == want_n, tag
         assert np.array_equal(out.cpu().numpy(), np.stack([w[0] for w in want])), tag
     assert ws.guards_intact() == (True, True), f"{tag}: wrote in front of / behind its workspace"
+
+
+@pytest.mark.parametrize("name", ["voyager_64", "voy_soft8", "lte_soft8_head15"])
+def test_exact_sync_search_workspace_between_guards(oracle, name):
+    import torch
+
+    c = sync_reference.make_case(name)
+    want_err, want_cmp, want_best, _ = sync_reference.case_reference(oracle, name)
+    pc, table, config = make_table_config(c["code"], c["decode_type"])
+    dec = BatchDecoder(table, config)
+    n = len(c["hypotheses"])
+    ws = GuardedWorkspace(_lib.load().vit_hip_sync_search_workspace_bytes(dec._handle._h, n, c["T"], c["W"], c["head"], c["tail"]))
+    out = torch.full((3, 64), -1, dtype=torch.int32, device="cuda")
+    rc = sync_search_raw(dec, c, ws.ptr, ws.need, out[0], out[1], out[2])
+    assert rc == _lib.OK, (name, _lib.load().vit_hip_last_error())
+    host = out.cpu().numpy()
+    assert host[0, :n].tolist() == want_err.tolist() and host[1, :n].tolist() == want_cmp.tolist() and int(host[2, 0]) == want_best, name
+    assert (host[:2, n:] == -1).all() and (host[2, 1:] == -1).all(), name
+    assert ws.guards_intact() == (True, True), f"{name}: wrote in front of / behind its workspace"

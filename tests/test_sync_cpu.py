@@ -90,6 +90,33 @@ def test_needed_received_is_the_largest_index_read():
     assert ref.needed_received([(0, 0)], 9, 2, ref.MASK_3_4) == 12
 
 
+@pytest.mark.parametrize("name,errors,compared,winner", ref.RANK_SETS, ids=[r[0] for r in ref.RANK_SETS])
+def test_hand_written_rankings(name, errors, compared, winner):
+    """the sets tests/test_gpu_sync_kernels.py gives to sync_pick_kernel, with the winners spelled out in the list"""
+    assert len(errors) == len(compared) and 1 <= len(errors) <= ref.MAX_HYPOTHESES
+    assert all(0 <= e <= c < 2 ** 32 for e, c in zip(errors, compared))
+    assert ref.rank(errors, compared) == winner
+
+
+def test_hand_written_rankings_hold_their_premises():
+    """equal rates are equal and their denominators are not; the wrap pairs need the whole 64-bit product"""
+    sets = {name: (errors, compared, winner) for name, errors, compared, winner in ref.RANK_SETS}
+    e, c, w = sets["equal rates, other denominators"]
+    tied = [i for i in range(len(e)) if e[i] * c[w] == e[w] * c[i]]
+    assert tied == [1, 3, 5] and len({c[i] for i in tied}) == 3
+    low = 0xFFFFFFFF
+    for ea, ca, eb, cb in (ref.WRAP_MORE_ERRORS, ref.WRAP_FEWER_COMPARED):
+        assert max(ea, ca, eb, cb) < 2 ** 32 and abs(ea - eb) + abs(ca - cb) == 1
+        assert ea * cb < eb * ca and (ea * cb) & low > (eb * ca) & low
+    ea, ca, eb, cb = ref.WRAP_EQUAL_LOW
+    assert ea * cb < eb * ca and (ea * cb) & low == (eb * ca) & low
+    # in the list the better of each pair stands behind the worse: a ranking that sees a tie, or the other order, names index 0
+    for name in ("one more error, low halves the other way", "one compared fewer, low halves the other way", "products 2^32 apart"):
+        assert sets[name][2] == 1
+    e, c, w = sets["64, the winner last"]
+    assert len(e) == 64 and w == 63 and sum(ei * c[w] <= e[w] * ci for ei, ci in zip(e, c)) == 1      # unique
+
+
 def test_ranking_rule():
     assert ref.rank([5, 5, 4], [100, 100, 100]) == 2
     assert ref.rank([5, 5, 5], [100, 100, 100]) == 0                  # a tie: the lower index
@@ -131,7 +158,7 @@ def test_the_reference_finds_the_truth(oracle, name):
     c = ref.make_case(name)
     code, hyps, truth = c["code"], c["hypotheses"], c["truth"]
     errors, compared, best, decoded = ref.case_reference(oracle, name)
-    assert ref.skip_bits(code.K) == {"is95": 8, "cassini": 16}.get(name, 8)
+    assert ref.skip_bits(code.K) == {"is95": 8, "cassini": 16, "k11_lds2": 16}.get(name, 8)
     assert ref.equivalent(code, hyps[best], truth), (hyps[best], truth)
     others = [i for i in range(len(hyps)) if not ref.equivalent(code, hyps[i], truth)]
     assert others and all(compared > 0)
@@ -141,19 +168,94 @@ def test_the_reference_finds_the_truth(oracle, name):
     if ref.is_transparent(code) and len(twins) == 2:
         assert errors[twins[0]] == errors[twins[1]] and compared[twins[0]] == compared[twins[1]]
         assert best == min(twins)
-        assert np.array_equal(decoded[twins[0]] ^ 1, decoded[twins[1]])
+        if name == "voy34_hard8":
+            # hard decisions behind a puncturing mask leave codewords that agree with every symbol that is compared: both twins
+            # count no error at all, but the add-compare-select ties between such codewords go to the lower state, which an
+            # inversion does not preserve -- the inverted twin decodes five bits of another codeword (bits 253 .. 262 of 295)
+            assert errors[twins[0]] == 0 and np.count_nonzero((decoded[twins[0]] ^ 1) != decoded[twins[1]]) == 5
+        else:
+            assert np.array_equal(decoded[twins[0]] ^ 1, decoded[twins[1]])
     else:
         assert twins == [c["true_index"]] == [best]
     tx = c["tx_bits"][c["head"]:c["T"] - c["tail"]]
     assert np.array_equal(decoded[c["true_index"]], tx)
 
 
-def test_cases_cover_what_they_claim():
+def test_cases_cover_what_they_claim(oracle):
     assert ref.is_transparent(COMMON_CODES[ref.VOYAGER]) and ref.is_transparent(COMMON_CODES[ref.IS95])
+    # every width is searched, at R = 2, 3 and 4, with and without a mask
+    assert {(ref.make_case(n)["decode_type"], ref.make_case(n)["code"].R) for n in ref.CPU_CASES} >= {
+        ("SOFT16", 2), ("SOFT16", 3), ("SOFT8", 2), ("SOFT8", 3), ("HARD8", 2), ("HARD8", 4)}
+    assert ref.make_case("voy34_hard8")["mask"] is not None and ref.make_case("voy34_hard8")["decode_type"] == "HARD8"
+    # HARD8: the channel's noise lands on the midpoint, so the hypotheses compare different numbers of symbols and the ranking's
+    # cross-multiplication has two denominators to work with
+    compared = ref.case_reference(oracle, "voy_hard8")[1]
+    assert len(set(compared.tolist())) > 1, compared
+    # a state narrower than a byte; a state of 10 bits out of two skipped bytes, on a code outside the stock table
+    k5, k11 = ref.make_case("k5")["code"], ref.make_case("k11_lds2")["code"]
+    assert (k5.K, ref.skip_bits(k5.K)) == (5, 8) and (k11.K, ref.skip_bits(k11.K)) == (11, 16) and k11 not in COMMON_CODES
+    assert [ref.make_case(n)["T"] for n in ("voy_soft8", "voy_hard8", "lte_soft8", "dab_hard8", "voy34_hard8")] == [352, 352, 357, 355, 359]
     assert ref.make_case("voyager_3_4")["T"] * 2 % len(ref.MASK_3_4) != 0          # T R is not a multiple of the period
     assert ref.make_case("voyager")["T"] == 48 + 4 * 64 + 48
     long = ref.make_case("voyager_long")
     assert (long["T"] - long["head"] - long["tail"]) % long["W"] != 0              # a longer last window
+
+
+def test_random_rankings_hold_their_premise():
+    """the seed of the random sets tests/test_gpu_sync_kernels.py ranks on the device: at least a third of the small-integer sets
+    have two or more hypotheses tied for the best rate, both ends of n occur, and index 0 is not the usual winner"""
+    sets = ref.random_rank_sets()
+    assert len(sets) == 2000 and all(1 <= len(e) == len(c) <= ref.MAX_HYPOTHESES and (e <= c).all() for e, c in sets)
+    small, wide = sets[0::2], sets[1::2]
+    assert all(int(c.max()) <= 6 for _, c in small) and any(int(c.max()) >= 2 ** 31 for _, c in wide)
+    ties = sum(1 for e, c in small if ref.tied_for_first(e, c) >= 2)
+    assert 3 * ties >= len(small), f"only {ties} of {len(small)} small-integer sets tie for first place"
+    assert any(len(e) == 1 for e, _ in sets) and any(len(e) == ref.MAX_HYPOTHESES for e, _ in sets)
+    winners = [ref.rank([int(x) for x in e], [int(x) for x in c]) for e, c in sets]
+    assert sum(1 for w in winners if w > 0) > len(sets) // 2
+
+
+@pytest.mark.parametrize("name", ["voyager_64", "voyager_64_reversed", "voyager_1"])
+def test_hypothesis_counts_on_the_reference(oracle, name):
+    """64 hypotheses (offsets over four steps, all 8 flag sets), the same list reversed and the truth alone: the winner is the true
+    alignment or the same one whole steps later, at half the rate of every other alignment; reversing the list moves the winner"""
+    c = ref.make_case(name)
+    hyps = c["hypotheses"]
+    errors, compared, best, _ = ref.case_reference(oracle, name)
+    assert len(hyps) == {"voyager_1": 1}.get(name, 64) and all(compared > 0)
+    assert ref.aligned(c, hyps[best]), hyps[best]
+    others = [i for i in range(len(hyps)) if not ref.aligned(c, hyps[i])]
+    assert len(others) == len(hyps) - {"voyager_1": 1}.get(name, 8)
+    assert all(2 * errors[best] * compared[i] <= errors[i] * compared[best] for i in others)
+    if name == "voyager_64_reversed":
+        forward = ref.case_reference(oracle, "voyager_64")
+        assert errors.tolist() == forward[0].tolist()[::-1] and best != forward[2]
+    if name == "voyager_1":
+        assert best == 0
+
+
+@pytest.mark.parametrize("name,residue", ref.SHAPE_CASES)
+def test_extension_and_window_shapes_on_the_reference(oracle, name, residue):
+    """the parameters of the extensions-and-windows test of tests/test_gpu_sync_search.py: they are what they claim, and the reference
+    decodes and counts them by itself and still names the truth"""
+    c = ref.make_case(name)
+    K, R = c["code"].K, c["code"].R
+    head, tail, W, T = c["head"], c["tail"], c["W"], c["T"]
+    assert K == 7 and head != tail and {head, tail} <= {K - 1, K, 2 * K + 1, 8 * (K - 1)}
+    assert W % head != 0 and W >= max(head, tail, 8)
+    assert (T - head - tail) % W in (1, W - 1) and (T - head - tail) // W >= 2
+    offset = (head + ref.skip_bits(K)) * R * np.dtype(c["pc"].soft_dtype).itemsize
+    assert ref.residue_class(offset) == residue, offset
+    errors, compared, best, decoded = ref.case_reference(oracle, name)
+    assert all(d.size == T - head - tail for d in decoded) and all(compared > 0) and all(errors <= compared)
+    assert ref.equivalent(c["code"], c["hypotheses"][best], c["truth"])
+
+
+def test_shape_cases_reach_every_way_of_reading_a_row():
+    assert {r for _, r in ref.SHAPE_CASES} == {"0 mod 16", "8 mod 16", "4 mod 8", "2 mod 4", "odd"}
+    cases = [ref.make_case(n) for n, _ in ref.SHAPE_CASES]
+    last = {(c["decode_type"], c["code"].R, (c["T"] - c["head"] - c["tail"]) % c["W"] == 1) for c in cases}
+    assert len(last) == 6                                              # every width with a remainder of 1 step and of W - 1
 
 
 def test_new_entry_points_resolve_and_reject_a_null_handle():
