@@ -48,6 +48,8 @@
  *   vit_hip_sync_build / vit_hip_sync_search  no reference counterpart: node synchronisation -- the streams of a set of alignment
  *                             hypotheses (symbol offset, puncture phase, I/Q rotation) from one received buffer, and their ranking by
  *                             that count in one call (rule below), with vit_hip_sync_search_workspace_bytes
+ *   vit_hip_marker_search     no reference counterpart: frame synchronisation -- the distance of a sync marker to the decoded bits,
+ *                             summed per phase of the frame period, and the phase and polarity it names (rule below)
  *
  * Semantics are those of the reference SCALAR strategy (strict '>' decision, wrapping error_t arithmetic,
  * renormalise only when new_metric[0] >= threshold): SURVEY.md section 8(a').  All results are bit-exact.
@@ -587,6 +589,50 @@ int vit_hip_sync_search(vit_hip_handle h, const void* d_received, size_t n_recei
                         size_t period_symbols, size_t kept_per_period, const vit_hip_sync_hypothesis* hypotheses, size_t n_hyp,
                         size_t T, size_t W, size_t head, size_t tail, void* d_workspace, size_t workspace_bytes, uint32_t* d_errors,
                         uint32_t* d_compared, uint32_t* d_best, vit_hip_stream_t stream);
+
+/* ---- frame synchronisation: the sync marker's phase and polarity -----------------------------------------------------------------
+ * The decode calls return a bit stream; a frame starts where the attached sync marker stands (CCSDS: the 32 bits 0x1ACFFC1D every
+ * frame length; DVB-S: 0x47 every 1632 bits), and the marker also settles the inversion that node synchronisation leaves open on a
+ * transparent code.  vit_hip_marker_search gives, for every bit phase of the frame period, the Hamming distance of the marker to the
+ * stream summed over all frames, and from that the phase, the polarity and a lock quality figure.  Rule, bit-exact:
+ *   - bits: bit t of a row is bit 7 - t%8 of byte t/8 (MSB-first, as chainback() writes them).  Row r starts at r * bytes_row_stride
+ *     (0 => ceil(n_bits/8); a non-zero stride is at least that).  Pad bits and what lies between rows are never interpreted, and no
+ *     byte at or behind ceil(n_bits/8) of a row is read;
+ *   - marker: marker_bits = m, 1 <= m <= 64.  Marker bit j (the j-th transmitted, 0 <= j < m) is bit m-1-j of `marker`; the bits of
+ *     `marker` above m must be 0;
+ *   - history: history_bits = hb, 0 <= hb <= 63.  d_history[r] is a uint64 whose low hb bits are the hb stream bits in front of bit 0
+ *     of row r, the latest of them bit 0 (NULL only with hb = 0).  It is to the marker what d_start_state is to
+ *     vit_hip_channel_errors_batch: a receiver counts the marker positions that straddle two calls;
+ *   - positions: p runs over -hb <= p <= n_bits - m (n_bits + hb >= m is required).  d(p) = #{ j : bit[p + j] != marker bit j },
+ *     negative indices read from the history;
+ *   - phases: period_bits = P >= 1, phase0 < P is the phase of position 0: position p belongs to phase (phase0 + p) mod P (the
+ *     mathematical mod: p may be negative).  distance[r][phase] = the sum of d(p) over the positions of that phase, count[r][phase]
+ *     their number;
+ *   - output: d_distance [rows][P] uint32 is required, d_count [rows][P] uint32 may be NULL.  Without VIT_HIP_MARKER_ACCUMULATE the
+ *     call OVERWRITES both (it zeroes them on `stream`, in a kernel, then adds integer partial sums: the result does not depend on
+ *     order, as in vit_hip_channel_errors_batch) and m * ceil((n_bits + hb) / P) < 2^32 is required, so that no sum wraps.  With the flag it adds
+ *     to what the buffers hold -- the running totals of a receiver, whose overflow the caller answers for;
+ *   - lock: d_lock [rows] (may be NULL; under ACCUMULATE it needs d_count) is computed from the totals as they stand after this
+ *     call.  Candidate (phase, upright) has errors = distance[phase], compared = m * count[phase]; (phase, inverted) has errors =
+ *     compared - distance[phase].  a beats b iff compared_a > 0 and (compared_b == 0 or errors_a compared_b < errors_b compared_a,
+ *     in 64-bit integers) -- the rule of d_best of vit_hip_sync_search; on a tie the lower phase wins, and at one phase upright
+ *     before inverted.  inverted = 1: the caller complements the decoded bytes.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL required pointer (d_count NULL with
+ * d_lock under ACCUMULATE), m outside 1 .. 64 or marker bits above m, hb > 63 or d_history NULL with hb > 0, n_bits + hb < m,
+ * n_bits >= 2^32 - 64, P = 0, P >= 2^31, phase0 >= P, a stride that is too small, unknown flag bits, the overflow bound above (and
+ * more than 2^31 - 1 rows).  rows = 0 returns VIT_HIP_OK with no work.
+ * A batch call like the others: it only enqueues kernels on `stream` (one that zeroes the totals unless they accumulate, the search,
+ * the pick when d_lock is given), allocates nothing, synchronises nothing, can be captured into a hipGraph, and reads the handle only
+ * for its device.
+ * Out of scope: an aperiodic "first hit under a threshold" search; markers longer than 64 bits; masked patterns such as DVB-S's
+ * 0x47 x 7, 0xB8 as ONE pattern -- such a caller searches 0x47 at P = 1632, where the right phase has an error rate of about 1/8
+ * against about 1/2 elsewhere, or at P = 13056. */
+#define VIT_HIP_MARKER_ACCUMULATE 1u  /* add to the totals in d_distance / d_count instead of overwriting them */
+typedef struct vit_hip_marker_lock { uint32_t phase, inverted, errors, compared; } vit_hip_marker_lock;
+int vit_hip_marker_search(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_row_stride, size_t rows, size_t n_bits,
+                          uint64_t marker, unsigned marker_bits, const uint64_t* d_history, unsigned history_bits,
+                          size_t period_bits, size_t phase0, unsigned flags, uint32_t* d_distance, uint32_t* d_count,
+                          vit_hip_marker_lock* d_lock, vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

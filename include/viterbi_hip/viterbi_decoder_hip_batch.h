@@ -164,6 +164,18 @@ public:
                                   window_or_default(window), extension(head), extension(tail), d_workspace, workspace_size, d_errors,
                                   d_compared, d_best, stream), "vit_hip_sync_search");
     }
+    // frame synchronisation (vit_hip_marker_search): the distance of a sync marker of marker_bits <= 64 bits to every bit position of
+    // rows of decoded bytes (MSB-first; bytes_row_stride 0: packed), summed per phase (phase0 + position) mod period_bits into
+    // d_distance / d_count [rows][period_bits] (d_count may be nullptr), and into d_lock [rows] (may be nullptr) the phase and
+    // polarity no other beats.  d_history [rows] holds the history_bits <= 63 stream bits in front of bit 0 of each row, the latest in
+    // bit 0.  flags: 0 overwrites the totals, VIT_HIP_MARKER_ACCUMULATE adds to them (a receiver's running totals).
+    void marker_search(const uint8_t* d_bytes, size_t rows, size_t n_bits, uint64_t marker, unsigned marker_bits, size_t period_bits,
+                       uint32_t* d_distance, uint32_t* d_count = nullptr, vit_hip_marker_lock* d_lock = nullptr, size_t phase0 = 0,
+                       const uint64_t* d_history = nullptr, unsigned history_bits = 0, unsigned flags = 0, size_t bytes_row_stride = 0,
+                       void* stream = nullptr) {
+        check(vit_hip_marker_search(m_hip, d_bytes, bytes_row_stride, rows, n_bits, marker, marker_bits, d_history, history_bits,
+                                    period_bits, phase0, flags, d_distance, d_count, d_lock, stream), "vit_hip_marker_search");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -34,6 +34,7 @@ EXPORTS = [
     "vit_hip_streams_workspace_bytes", "vit_hip_decode_streams",
     "vit_hip_encode_batch", "vit_hip_channel_errors_batch",
     "vit_hip_sync_build", "vit_hip_sync_search_workspace_bytes", "vit_hip_sync_search",
+    "vit_hip_marker_search",
 ]
 
 
@@ -73,6 +74,7 @@ STREAM_BEGIN, STREAM_END = 1, 2
 ENCODE_TAIL, ENCODE_TAIL_BITING = 1, 2
 SYNC_SWAP_PAIRS, SYNC_NEGATE_EVEN, SYNC_NEGATE_ODD = 1, 2, 4
 SYNC_MAX_HYPOTHESES = 64
+MARKER_ACCUMULATE = 1
 
 
 class VitHipSyncHypothesis(C.Structure):
@@ -145,6 +147,7 @@ def load():
     L.vit_hip_sync_search_workspace_bytes.restype = sz
     L.vit_hip_sync_search_workspace_bytes.argtypes = [vp, sz, sz, sz, sz, sz]
     L.vit_hip_sync_search.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(VitHipSyncHypothesis), sz, sz, sz, sz, sz, vp, sz, vp, vp, vp, vp]
+    L.vit_hip_marker_search.argtypes = [vp, vp, sz, sz, sz, C.c_uint64, C.c_uint, vp, C.c_uint, sz, sz, C.c_uint, vp, vp, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -11,6 +11,8 @@
 //   vit_encode.hip   the encoder on the caller's bytes and the re-encoded channel symbol error count (kernels_enc.hpp)
 //   vit_sync.hip     node synchronisation: the streams of a set of alignment hypotheses and their ranking, around the C ABI's own
 //                    vit_hip_decode_streams and the body of vit_hip_channel_errors_batch, declared below (kernels_sync.hpp)
+//   vit_marker.hip   frame synchronisation: the sync marker's distance per phase of the frame period, on the caller's bytes
+//                    (kernels_marker.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

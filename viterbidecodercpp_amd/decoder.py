@@ -796,6 +796,52 @@ class BatchDecoder:
             ws.numel() * ws.element_size(), _ptr(err), _ptr(cmp), _ptr(best), self._stream()))
         return err, cmp, best
 
+    def marker_search(self, bytes, n_bits: int, marker: int, marker_bits: int, period: int, phase0: int = 0, history=None,
+                      history_bits: int = 0, out=None, accumulate=False):
+        """frame synchronisation (vit_hip_marker_search): the Hamming distance of the sync marker (`marker_bits` bits, the first
+        transmitted in the highest; frame_sync.CCSDS_ASM, DVB_SYNC) to every bit position of the decoded `bytes` -- uint8 CUDA, one
+        row or [rows][>= ceil(n_bits/8)] with its row stride, MSB-first as the decode calls write them --, summed per phase of the
+        frame period: position p belongs to phase (phase0 + p) mod period.  history [rows] (ints or a tensor): the `history_bits`
+        <= 63 stream bits in front of bit 0, the latest in bit 0, so that positions straddling two calls are counted.  returns
+        (distance, count, lock): int32 CUDA tensors [rows][period], [rows][period] and [rows][4] = (phase, inverted, errors,
+        compared) of the candidate with the lowest errors / compared (compared = marker_bits * count; inverted: errors = compared -
+        distance; the lower phase, then upright, on a tie).  out = (distance, count, lock) reuses those tensors; with
+        accumulate=True the call adds to the totals they hold and the lock is that of the totals.  Nothing is copied to the host."""
+        t = self.torch
+        if bytes.dtype != t.uint8 or not bytes.is_cuda or bytes.dim() not in (1, 2) or (bytes.numel() and bytes.stride(-1) != 1):
+            raise ValueError("bytes must be a uint8 CUDA tensor, one row or [rows][>= ceil(n_bits/8)] with contiguous rows")
+        n_bits, period, nb = int(n_bits), int(period), (int(n_bits) + 7) // 8
+        rows = 1 if bytes.dim() == 1 else int(bytes.shape[0])
+        if bytes.shape[-1] < nb:
+            raise ValueError(f"{n_bits} bits need {nb} bytes per row")
+        stride = int(bytes.stride(0)) if bytes.dim() == 2 and rows > 1 else 0
+        if period < 1 or period >= 1 << 31:
+            raise ValueError("period must be 1 .. 2^31 - 1")
+        hist = None
+        if history_bits:
+            if history is None:
+                raise ValueError("history_bits > 0 needs the history words")
+            if t.is_tensor(history):
+                hist = history.to(device=self.device, dtype=t.int64).reshape(-1).contiguous()
+            else:
+                words = np.asarray([int(x) for x in np.asarray(history, dtype=object).reshape(-1)], dtype=np.uint64)
+                hist = t.from_numpy(words.view(np.int64)).to(self.device)
+            if hist.numel() != rows:
+                raise ValueError("history must hold one word per row")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True adds to the totals of out=(distance, count, lock)")
+            out = (t.empty((rows, period), dtype=t.int32, device=self.device), t.empty((rows, period), dtype=t.int32, device=self.device),
+                   t.empty((rows, 4), dtype=t.int32, device=self.device))
+        distance, count, lock = out
+        for x, n in ((distance, rows * period), (count, rows * period), (lock, rows * 4)):
+            if x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != n:
+                raise ValueError(f"out must be contiguous int32 CUDA tensors of [{rows}][{period}], [{rows}][{period}] and [{rows}][4]")
+        _lib.check(_lib.load().vit_hip_marker_search(
+            self._handle._h, _ptr(bytes), stride, rows, n_bits, int(marker), int(marker_bits), _ptr(hist), int(history_bits), period,
+            int(phase0), _lib.MARKER_ACCUMULATE if accumulate else 0, _ptr(distance), _ptr(count), _ptr(lock), self._stream()))
+        return distance, count, lock
+
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The
         workspace is an array of independent slabs of `workspace_tile_frames` frames (vit_hip_info), so `frames` frames

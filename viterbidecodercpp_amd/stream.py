@@ -38,14 +38,21 @@ class MultiStreamDecoder:
     compared) of the re-encoded channel symbol error count (BatchDecoder.channel_errors) over every trellis step whose bit has been
     emitted so far -- each step exactly once, however the pushes were cut; finish() adds the K-1 tail steps.  One more launch and
     one small read-back per internal call for all streams; the last K-1 emitted bits are carried as the next call's start state.
-    Off (the default), nothing changes."""
+    Off (the default), nothing changes.
+
+    marker=(value, bits) with period=P (frame_sync.CCSDS_ASM, DVB_SYNC): the object also keeps the running per-phase totals of the
+    frame marker search (BatchDecoder.marker_search) over everything it emits: `.marker_totals` = (distance, count), int64 arrays
+    [n_streams][P], and `.marker_lock`, per stream the (phase, inverted, errors, compared) those totals name.  Every marker position
+    of the whole emitted stream is counted exactly once, however the pushes were cut -- the last bits-1 emitted bits are carried as
+    the next call's history --, and a phase is counted from the stream's first emitted bit.  One more accumulate-mode search per
+    internal call; the totals live on the device as 32-bit counters (they wrap past 2^32 - 1).  Off (the default), nothing changes."""
 
     # how the errors word it; StreamDecoder has its own
     _RULE = "n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams"
     _SHAPE, _FINISHED, _EMPTY = "[n_streams][steps][R]", "the streams are finished", "empty streams"
 
     def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
-                 channel_errors: bool = False):
+                 channel_errors: bool = False, marker=None, period: int = None):
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
@@ -65,6 +72,18 @@ class MultiStreamDecoder:
         if channel_errors:
             self._totals = (np.zeros(self.n_streams, dtype=np.int64), np.zeros(self.n_streams, dtype=np.int64))
             self._state = np.zeros(self.n_streams, dtype=np.int64)    # the last K-1 emitted bits, as a decoder state
+        self._marker = None
+        if marker is not None:
+            value, bits = int(marker[0]), int(marker[1])
+            if period is None or not 1 <= int(period) < 1 << 31 or not 1 <= bits <= 64 or value >> bits:
+                raise ValueError("marker=(value, bits) needs 1 <= bits <= 64, no bit of value above them, and period=P >= 1")
+            t = decoder.torch
+            self._marker = (value, bits, int(period))
+            self._marker_out = (t.zeros((self.n_streams, int(period)), dtype=t.int32, device=decoder.device),
+                                t.zeros((self.n_streams, int(period)), dtype=t.int32, device=decoder.device),
+                                t.zeros((self.n_streams, 4), dtype=t.int32, device=decoder.device))
+            self._emitted = 0                                         # bits the internal calls have emitted, per stream
+            self._recent = np.zeros((self.n_streams, 0), dtype=np.uint8)    # the last bits-1 of them
 
     @property
     def channel_errors(self):
@@ -79,6 +98,31 @@ class MultiStreamDecoder:
                                       symbol_frame_stride=self._buf.shape[1] * dec.R)
         self._totals = (self._totals[0] + err.cpu().numpy(), self._totals[1] + cmp.cpu().numpy())
         self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits], dec.K)
+
+    def _no_marker(self):
+        if self._marker is None:
+            raise AttributeError("this receiver was made without marker=(value, bits) and period=P")
+
+    @property
+    def marker_totals(self):
+        self._no_marker()
+        return tuple(x.cpu().numpy().view(np.uint32).astype(np.int64) for x in self._marker_out[:2])
+
+    @property
+    def marker_lock(self):
+        self._no_marker()
+        return [tuple(int(v) for v in row) for row in self._marker_out[2].cpu().numpy().view(np.uint32)]
+
+    def _search(self, out, n_bits):
+        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted; the history is what was emitted before them"""
+        value, m, P = self._marker
+        hb = self._recent.shape[1]
+        if n_bits + hb >= m:
+            history = [int("".join(map(str, row)), 2) if hb else 0 for row in self._recent]
+            self.decoder.marker_search(out, n_bits, value, m, P, self._emitted % P, history, hb, out=self._marker_out, accumulate=True)
+        bits = np.concatenate([self._recent, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
+        self._recent = bits[:, max(bits.shape[1] - (m - 1), 0):]
+        self._emitted += n_bits
 
     def _append(self, symbols):
         if symbols is None:
@@ -105,6 +149,8 @@ class MultiStreamDecoder:
         self.calls.append((steps, self._first, end))
         if self._totals is not None:
             self._count(out, n_bits, end)
+        if self._marker is not None:
+            self._search(out, n_bits)
         self._first = False
         # whole bytes only: the rest waits in the carry, which the last call flushes
         bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
@@ -142,13 +188,24 @@ class MultiStreamDecoder:
 
 class StreamDecoder(MultiStreamDecoder):
     """MultiStreamDecoder for ONE long stream: push() and finish() take any tensor of whole trellis steps ([steps][R], flat, or a view
-    that is not contiguous) and return `bytes`; `.channel_errors` (with channel_errors=True) is a pair of ints."""
+    that is not contiguous) and return `bytes`; `.channel_errors` (with channel_errors=True) is a pair of ints, `.marker_totals` (with
+    marker and period) a pair of [P] arrays and `.marker_lock` one (phase, inverted, errors, compared)."""
 
     _RULE = "window, head, tail outside the argument rule of vit_hip_decode_stream"
     _SHAPE, _FINISHED, _EMPTY = "[steps][R]", "the stream is finished", "an empty stream"
 
-    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False):
-        super().__init__(decoder, 1, window, head, tail, channel_errors)
+    def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False,
+                 marker=None, period: int = None):
+        super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period)
+
+    @property
+    def marker_totals(self):
+        distance, count = super().marker_totals
+        return distance[0], count[0]
+
+    @property
+    def marker_lock(self):
+        return super().marker_lock[0]
 
     @property
     def channel_errors(self):
