@@ -50,6 +50,9 @@
  *                             that count in one call (rule below), with vit_hip_sync_search_workspace_bytes
  *   vit_hip_marker_search     no reference counterpart: frame synchronisation -- the distance of a sync marker to the decoded bits,
  *                             summed per phase of the frame period, and the phase and polarity it names (rule below)
+ *   vit_hip_frames_extract    no reference counterpart: frame extraction -- the frames of the decoded bits cut at that lock, each on a
+ *                             byte boundary, complemented, derandomised, the unfinished frame carried to the next call (rule below),
+ *                             with vit_hip_frames_capacity
  *
  * Semantics are those of the reference SCALAR strategy (strict '>' decision, wrapping error_t arithmetic,
  * renormalise only when new_metric[0] >= threshold): SURVEY.md section 8(a').  All results are bit-exact.
@@ -633,6 +636,52 @@ int vit_hip_marker_search(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes
                           uint64_t marker, unsigned marker_bits, const uint64_t* d_history, unsigned history_bits,
                           size_t period_bits, size_t phase0, unsigned flags, uint32_t* d_distance, uint32_t* d_count,
                           vit_hip_marker_lock* d_lock, vit_hip_stream_t stream);
+
+/* ---- frame extraction: aligned, derandomised frames cut at the marker lock ---------------------------------------------------------
+ * vit_hip_marker_search names the bit phase of the frame period at which the marker stands and the polarity; a frame almost never
+ * starts on a byte of the decoded rows.  vit_hip_frames_extract takes the rows of decoded bytes of one call and, per row, a carry --
+ * the bits of the frame the previous call left unfinished --, and writes every frame the two complete together, each from bit 0 of a
+ * byte on, and the new carry.  Rule, bit-exact, per row r, with P = period_bits:
+ *   - bits: bit t of any row, carry or frame is bit 7 - t%8 of byte t/8.  Row r starts at r * bytes_row_stride (0 => ceil(n_bits/8);
+ *     a non-zero stride is at least that); no byte at or behind ceil(n_bits/8) of a row is read;
+ *   - carry: c = d_carry_bits_in[r]; a value above P-1 reads as 0.  d_carry_in == NULL: every c = 0, and d_carry_bits_in is not
+ *     read.  The carry row r starts at r * carry_row_stride (0 => ceil((P-1)/8); a non-zero stride is at least that), in and out
+ *     alike; no byte at or behind ceil(c/8) of a carry row is read.  The logical stream S has total = c + n_bits bits: the c carry
+ *     bits, then the row's n_bits;
+ *   - phase0 < P is the phase of bit 0 of the ROW, the argument vit_hip_marker_search takes;
+ *   - lock: read on the device from d_lock[r], the struct vit_hip_marker_search writes: phi = d_lock[r].phase mod P, inv =
+ *     d_lock[r].inverted != 0 (errors and compared are not read).  Whatever the memory holds, the kernel stays inside its buffers;
+ *   - first frame start: skip = (phi + c - phase0) mod P (the mathematical mod).  A carry that begins on a frame start gives skip = 0;
+ *     after a re-lock to another phase skip > 0, and the stale partial frame is dropped with the bits in front of the new start;
+ *   - counts: skip >= total: nf = 0, rem = 0; else nf = (total - skip) div P, rem = (total - skip) mod P.  d_n_frames[r] = nf.
+ *     nf <= ceil(n_bits / P) = vit_hip_frames_capacity(n_bits, P); max_frames must be at least that;
+ *   - frame f < nf: F[j] = S[skip + f P + j] ^ inv, 0 <= j < P;
+ *   - marker distance: marker_bits = m (0: off; m <= 64, m <= P, marker bit j is bit m-1-j of `marker` as in vit_hip_marker_search):
+ *     d_marker_errors[r * max_frames + f] (uint32, may be NULL) = #{ j < m : F[j] != marker bit j } -- the per-frame figure a
+ *     flywheel needs;
+ *   - output: drop_bits = d < P, Q = P - d: output bit k = F[d + k] ^ pad bit k, 0 <= k < Q, with d_pad [ceil(Q/8)] device bytes shared
+ *     by all rows (NULL: none; the CCSDS pseudo-random sequence, say), packed into ceil(Q/8) bytes at d_frames + (r * max_frames + f) *
+ *     frame_stride_bytes (0 => ceil(Q/8); a non-zero stride is at least that); the pad bits of the last byte are 0.  Bytes behind a
+ *     frame inside its stride are NOT written, frames f >= nf (and their marker distances) are NOT written;
+ *   - new carry: d_carry_out row r receives the raw bits S[skip + nf P, total) -- not complemented, not padded: the lock may change
+ *     -- from bit 0 of byte 0 on, the pad bits of the last byte 0; bytes behind ceil(rem/8) are not written.  d_carry_bits_out[r] =
+ *     rem.  In and out are distinct buffers that overlap neither each other nor d_bytes (the caller ping-pongs them): one launch reads
+ *     the old carry and writes the new one with no ordering between workgroups.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for NULL d_bytes, d_lock, d_frames, d_n_frames,
+ * d_carry_out or d_carry_bits_out, d_carry_in without d_carry_bits_in, P < 8 or P >= 2^31, phase0 >= P, d >= P, m > 64, m > P or
+ * marker bits above m, n_bits = 0 or n_bits >= 2^32 - 64, a stride that is too small, max_frames below the capacity, more than
+ * 2^31 - 1 rows.  rows = 0 returns VIT_HIP_OK with no work.
+ * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, synchronises nothing, can be
+ * captured into a hipGraph, and reads the handle only for its device.
+ * Out of scope: a lock threshold or flywheel policy (the caller decides from d_marker_errors whether to trust a frame); frames of
+ * varying length; DVB-S's inverted every-eighth sync byte as part of extraction. */
+size_t vit_hip_frames_capacity(size_t n_bits, size_t period_bits);   /* ceil(n_bits / period_bits); 0 for period_bits = 0 */
+int vit_hip_frames_extract(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_row_stride, size_t rows, size_t n_bits,
+                           size_t period_bits, size_t phase0, const vit_hip_marker_lock* d_lock, const uint8_t* d_carry_in,
+                           const uint32_t* d_carry_bits_in, size_t carry_row_stride, uint64_t marker, unsigned marker_bits,
+                           size_t drop_bits, const uint8_t* d_pad, uint8_t* d_frames, size_t frame_stride_bytes, size_t max_frames,
+                           uint32_t* d_n_frames, uint32_t* d_marker_errors, uint8_t* d_carry_out, uint32_t* d_carry_bits_out,
+                           vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

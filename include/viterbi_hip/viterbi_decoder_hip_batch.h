@@ -176,6 +176,24 @@ public:
         check(vit_hip_marker_search(m_hip, d_bytes, bytes_row_stride, rows, n_bits, marker, marker_bits, d_history, history_bits,
                                     period_bits, phase0, flags, d_distance, d_count, d_lock, stream), "vit_hip_marker_search");
     }
+    // frame extraction (vit_hip_frames_extract): the frames of rows of decoded bytes cut at the lock marker_search wrote (d_lock, read on
+    // the device), each from bit 0 of a byte on at d_frames + (row * max_frames + f) * frame_stride_bytes: complemented under an
+    // inverted lock, the first drop_bits bits (the marker) dropped, d_pad [ceil((period_bits - drop_bits) / 8)] (the randomiser; may be
+    // nullptr) XORed off.  d_n_frames [rows] receives the frames completed, d_marker_errors [rows][max_frames] (may be nullptr, with
+    // marker_bits 0: off) the marker bits of each that differ, d_carry_out / d_carry_bits_out the unfinished frame's raw bits, which
+    // the next call takes as d_carry_in / d_carry_bits_in (nullptr: none).  max_frames >= frames_capacity(n_bits, period_bits).
+    static size_t frames_capacity(size_t n_bits, size_t period_bits) { return vit_hip_frames_capacity(n_bits, period_bits); }
+    void frames_extract(const uint8_t* d_bytes, size_t rows, size_t n_bits, size_t period_bits, size_t phase0,
+                        const vit_hip_marker_lock* d_lock, const uint8_t* d_carry_in, const uint32_t* d_carry_bits_in, uint8_t* d_frames,
+                        size_t max_frames, uint32_t* d_n_frames, uint8_t* d_carry_out, uint32_t* d_carry_bits_out,
+                        uint32_t* d_marker_errors = nullptr, uint64_t marker = 0, unsigned marker_bits = 0, size_t drop_bits = 0,
+                        const uint8_t* d_pad = nullptr, size_t bytes_row_stride = 0, size_t carry_row_stride = 0,
+                        size_t frame_stride_bytes = 0, void* stream = nullptr) {
+        check(vit_hip_frames_extract(m_hip, d_bytes, bytes_row_stride, rows, n_bits, period_bits, phase0, d_lock, d_carry_in,
+                                     d_carry_bits_in, carry_row_stride, marker, marker_bits, drop_bits, d_pad, d_frames, frame_stride_bytes,
+                                     max_frames, d_n_frames, d_marker_errors, d_carry_out, d_carry_bits_out, stream),
+              "vit_hip_frames_extract");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

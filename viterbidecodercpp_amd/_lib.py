@@ -35,6 +35,7 @@ EXPORTS = [
     "vit_hip_encode_batch", "vit_hip_channel_errors_batch",
     "vit_hip_sync_build", "vit_hip_sync_search_workspace_bytes", "vit_hip_sync_search",
     "vit_hip_marker_search",
+    "vit_hip_frames_capacity", "vit_hip_frames_extract",
 ]
 
 
@@ -148,6 +149,9 @@ def load():
     L.vit_hip_sync_search_workspace_bytes.argtypes = [vp, sz, sz, sz, sz, sz]
     L.vit_hip_sync_search.argtypes = [vp, vp, sz, vp, sz, sz, C.POINTER(VitHipSyncHypothesis), sz, sz, sz, sz, sz, vp, sz, vp, vp, vp, vp]
     L.vit_hip_marker_search.argtypes = [vp, vp, sz, sz, sz, C.c_uint64, C.c_uint, vp, C.c_uint, sz, sz, C.c_uint, vp, vp, vp, vp]
+    L.vit_hip_frames_capacity.restype = sz
+    L.vit_hip_frames_capacity.argtypes = [sz, sz]
+    L.vit_hip_frames_extract.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, C.c_uint64, C.c_uint, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -13,6 +13,8 @@
 //                    vit_hip_decode_streams and the body of vit_hip_channel_errors_batch, declared below (kernels_sync.hpp)
 //   vit_marker.hip   frame synchronisation: the sync marker's distance per phase of the frame period, on the caller's bytes
 //                    (kernels_marker.hpp)
+//   vit_frames.hip   frame extraction: the frames of the caller's bytes cut at that lock, byte-aligned, with the carry between calls
+//                    (kernels_frames.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

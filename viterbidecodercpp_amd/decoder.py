@@ -842,6 +842,68 @@ class BatchDecoder:
             int(phase0), _lib.MARKER_ACCUMULATE if accumulate else 0, _ptr(distance), _ptr(count), _ptr(lock), self._stream()))
         return distance, count, lock
 
+    def frames_capacity(self, n_bits: int, period: int) -> int:
+        """the most frames one frames_extract call over n_bits bits per row can complete: ceil(n_bits / period)"""
+        return int(_lib.load().vit_hip_frames_capacity(int(n_bits), int(period)))
+
+    def frames_extract(self, bytes, n_bits: int, period: int, phase0: int, lock, carry=None, carry_bits=None, marker: int = 0,
+                       marker_bits: int = 0, drop_bits: int = 0, pad=None, max_frames: int = None, out=None):
+        """frame extraction (vit_hip_frames_extract): the frames of the decoded `bytes` -- uint8 CUDA, one row or [rows][>=
+        ceil(n_bits/8)], MSB-first, bit 0 at phase `phase0` of the frame period -- cut at `lock`, the int32 [rows][4] tensor
+        marker_search returns (read on the device: phase and inverted).  carry / carry_bits: the uint8 [rows][>= ceil((period-1)/8)]
+        and int32 [rows] the previous call returned as carry_out / carry_bits_out (None: nothing carried).  A frame is complemented
+        under an inverted lock, loses its first `drop_bits` bits (the marker) and is XORed with `pad`, uint8 CUDA [ceil(Q/8)] for its Q
+        = period - drop_bits output bits (frame_sync.ccsds_randomizer; None: none).  returns (frames, n_frames, marker_errors,
+        carry_out, carry_bits_out): uint8 [rows][max_frames][ceil(Q/8)] of which the first n_frames[r] (int32 [rows]) of row r are
+        written, int32 [rows][max_frames] = the bits of `marker` (marker_bits <= 64; 0: off, and None is returned) each written frame
+        differs in, and the unfinished frame's raw bits with their number.  max_frames defaults to frames_capacity(n_bits, period).
+        out = the same five reuses those tensors (frames may have a larger last dimension: its stride is the frame stride); carry
+        and carry_out must be distinct and have the same row stride.  Nothing is copied to the host."""
+        t = self.torch
+        if bytes.dtype != t.uint8 or not bytes.is_cuda or bytes.dim() not in (1, 2) or (bytes.numel() and bytes.stride(-1) != 1):
+            raise ValueError("bytes must be a uint8 CUDA tensor, one row or [rows][>= ceil(n_bits/8)] with contiguous rows")
+        n_bits, period, drop_bits, marker_bits = int(n_bits), int(period), int(drop_bits), int(marker_bits)
+        rows = 1 if bytes.dim() == 1 else int(bytes.shape[0])
+        if bytes.shape[-1] < (n_bits + 7) // 8:
+            raise ValueError(f"{n_bits} bits need {(n_bits + 7) // 8} bytes per row")
+        if not 8 <= period < 1 << 31 or not 0 <= drop_bits < period or n_bits < 1:
+            raise ValueError("period must be 8 .. 2^31 - 1, drop_bits below it, n_bits at least 1")
+        stride = int(bytes.stride(0)) if bytes.dim() == 2 and rows > 1 else 0
+        qb, cb = (period - drop_bits + 7) // 8, (period - 1 + 7) // 8
+        cap = self.frames_capacity(n_bits, period)
+        max_frames = cap if max_frames is None else int(max_frames)
+        if lock.dtype != t.int32 or not lock.is_cuda or not lock.is_contiguous() or lock.numel() != rows * 4:
+            raise ValueError(f"lock must be the contiguous int32 CUDA tensor [{rows}][4] marker_search returns")
+        if out is None:
+            out = (t.empty((rows, max_frames, qb), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device),
+                   t.empty((rows, max_frames), dtype=t.int32, device=self.device) if marker_bits else None,
+                   t.empty((rows, cb), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device))
+        frames, n_frames, marker_errors, carry_out, carry_bits_out = out
+        if (frames.dtype != t.uint8 or not frames.is_cuda or frames.dim() != 3 or tuple(frames.shape[:2]) != (rows, max_frames)
+                or frames.shape[2] < qb or frames.stride(2) != 1 or (rows > 1 and frames.stride(0) != max_frames * frames.stride(1))):
+            raise ValueError(f"out[0] must be a uint8 CUDA tensor [{rows}][{max_frames}][>= {qb}] with evenly spaced frames")
+        for x, n in ((n_frames, rows), (marker_errors, rows * max_frames), (carry_bits_out, rows)):
+            if x is not None and (x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != n):
+                raise ValueError(f"out must hold contiguous int32 CUDA tensors of [{rows}], [{rows}][{max_frames}] and [{rows}]")
+        for x in (carry_out, carry):
+            if x is not None and (x.dtype != t.uint8 or not x.is_cuda or x.dim() != 2 or x.shape[0] != rows or x.shape[1] < cb
+                                  or x.stride(1) != 1):
+                raise ValueError(f"a carry must be a uint8 CUDA tensor [{rows}][>= {cb}] with contiguous rows")
+        cstride = int(carry_out.stride(0)) if rows > 1 else int(carry_out.shape[1])
+        if carry is not None:
+            if (carry_bits is None or carry_bits.dtype != t.int32 or not carry_bits.is_cuda or not carry_bits.is_contiguous()
+                    or carry_bits.numel() != rows):
+                raise ValueError(f"carry needs carry_bits, a contiguous int32 CUDA tensor [{rows}]")
+            if (int(carry.stride(0)) if rows > 1 else int(carry.shape[1])) != cstride or carry.data_ptr() == carry_out.data_ptr():
+                raise ValueError("carry and carry_out must be distinct tensors with the same row stride")
+        if pad is not None and (pad.dtype != t.uint8 or not pad.is_cuda or not pad.is_contiguous() or pad.numel() < qb):
+            raise ValueError(f"pad must be a contiguous uint8 CUDA tensor of at least {qb} bytes")
+        _lib.check(_lib.load().vit_hip_frames_extract(
+            self._handle._h, _ptr(bytes), stride, rows, n_bits, period, int(phase0), _ptr(lock), _ptr(carry),
+            _ptr(carry_bits) if carry is not None else None, cstride, int(marker), marker_bits, drop_bits, _ptr(pad), _ptr(frames),
+            int(frames.stride(1)), max_frames, _ptr(n_frames), _ptr(marker_errors), _ptr(carry_out), _ptr(carry_bits_out), self._stream()))
+        return frames, n_frames, marker_errors, carry_out, carry_bits_out
+
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The
         workspace is an array of independent slabs of `workspace_tile_frames` frames (vit_hip_info), so `frames` frames

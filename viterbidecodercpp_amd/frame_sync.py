@@ -1,8 +1,10 @@
-"""Frame synchronisation (BatchDecoder.marker_search / vit_hip_marker_search): the stock sync markers and the rule in numpy.
+"""Frame synchronisation (BatchDecoder.marker_search / vit_hip_marker_search) and frame extraction (BatchDecoder.frames_extract /
+vit_hip_frames_extract): the stock sync markers, the CCSDS randomiser and the rules in numpy.
 
 The device call gives, for every bit phase of the frame period, the Hamming distance of the marker to the decoded bit stream summed
 over all frames, and the (phase, polarity) no other beats.  `marker_search_numpy` and `marker_lock_numpy` restate the rule of
-include/vit_hip.h on the host, as synth.channel_errors_numpy restates the channel symbol error count.
+include/vit_hip.h on the host, as synth.channel_errors_numpy restates the channel symbol error count.  `frames_extract_numpy` restates
+the cut of the stream into byte-aligned frames at that lock, one row at a time, on unpacked bits.
 """
 from __future__ import annotations
 
@@ -72,3 +74,40 @@ def marker_lock_numpy(distance, count, marker_bits: int) -> np.ndarray:
                     best = (phase, inverted, errors, compared)
         out[r] = best
     return out
+
+
+def ccsds_randomizer(n_bytes: int) -> np.ndarray:
+    """the first n_bytes bytes of the CCSDS pseudo-random sequence (x^8 + x^7 + x^5 + x^3 + 1, the register all ones at the first bit
+    behind the sync marker; period 255 bits): FF 48 0E C0 9A 0D 70 BC ...  With drop_bits = 32 it is the `pad` of frames_extract."""
+    s = [1] * 8
+    bits = np.empty(8 * int(n_bytes), dtype=np.uint8)
+    for i in range(bits.size):
+        bits[i] = s[0]
+        s = s[1:] + [s[0] ^ s[3] ^ s[5] ^ s[7]]
+    return np.packbits(bits)
+
+
+def frames_extract_numpy(row, n_bits: int, period: int, phase0: int, lock, carry=None, carry_bits: int = 0, marker: int = 0,
+                         marker_bits: int = 0, drop_bits: int = 0, pad=None):
+    """the rule of vit_hip_frames_extract for ONE row: row uint8 [>= ceil(n_bits/8)], lock = (phase, inverted, ...), carry uint8 [>=
+    ceil(carry_bits/8)] or None.  returns (frames uint8 [nf][ceil(Q/8)], marker_errors int64 [nf] or None with marker_bits = 0,
+    carry_out uint8 [ceil(rem/8)], rem)."""
+    n_bits, P, d, m = int(n_bits), int(period), int(drop_bits), int(marker_bits)
+    row = np.asarray(row, dtype=np.uint8).reshape(-1)
+    if not 8 <= P < 1 << 31 or not 0 <= int(phase0) < P or not 0 <= d < P or n_bits < 1 or row.size * 8 < n_bits or m > min(64, P):
+        raise ValueError("outside the argument rule of vit_hip_frames_extract")
+    c = int(carry_bits) if carry is not None else 0
+    c = 0 if c > P - 1 else c
+    before = np.unpackbits(np.asarray(carry, dtype=np.uint8).reshape(-1))[:c] if c else np.zeros(0, dtype=np.uint8)
+    S = np.concatenate([before, np.unpackbits(row)[:n_bits]])
+    phi, inv = int(lock[0]) % P, np.uint8(int(lock[1]) != 0)
+    skip = (phi + c - int(phase0)) % P
+    nf, rem = ((S.size - skip) // P, (S.size - skip) % P) if skip < S.size else (0, 0)
+    Q = P - d
+    F = S[skip:skip + nf * P].reshape(nf, P) ^ inv
+    errors = (F[:, :m] != marker_bit_array(marker, m)).sum(axis=1).astype(np.int64) if m else None
+    out = F[:, d:]
+    if pad is not None:
+        out = out ^ np.unpackbits(np.asarray(pad, dtype=np.uint8).reshape(-1))[:Q]
+    frames = np.packbits(out, axis=1) if nf else np.zeros((0, (Q + 7) // 8), dtype=np.uint8)
+    return frames, errors, np.packbits(S[S.size - rem:] if rem else S[:0]), rem

@@ -45,14 +45,23 @@ class MultiStreamDecoder:
     [n_streams][P], and `.marker_lock`, per stream the (phase, inverted, errors, compared) those totals name.  Every marker position
     of the whole emitted stream is counted exactly once, however the pushes were cut -- the last bits-1 emitted bits are carried as
     the next call's history --, and a phase is counted from the stream's first emitted bit.  One more accumulate-mode search per
-    internal call; the totals live on the device as 32-bit counters (they wrap past 2^32 - 1).  Off (the default), nothing changes."""
+    internal call; the totals live on the device as 32-bit counters (they wrap past 2^32 - 1).  Off (the default), nothing changes.
+
+    frames=True (needs marker and period >= 8): after the search of every internal call the object cuts the emitted bits into frames
+    on the device (BatchDecoder.frames_extract) at the lock as it stands after that call: each frame from bit 0 of a byte on,
+    complemented under an inverted lock, without its first frame_drop_bits bits (the marker, say), XORed with frame_pad (uint8,
+    ceil(Q/8) bytes for the Q = P - frame_drop_bits output bits: frame_sync.ccsds_randomizer).  The unfinished frame at the end of a
+    call stays on the device in one of two carry buffers and is completed by a later call, however the pushes were cut.
+    take_frames() returns, per stream, (uint8 [n][ceil(Q/8)], marker_errors int64 [n]) for the frames completed since the last
+    take; whether to trust a frame is the caller's decision, from its marker_errors.  Off (the default), nothing changes."""
 
     # how the errors word it; StreamDecoder has its own
     _RULE = "n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams"
     _SHAPE, _FINISHED, _EMPTY = "[n_streams][steps][R]", "the streams are finished", "empty streams"
 
     def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
-                 channel_errors: bool = False, marker=None, period: int = None):
+                 channel_errors: bool = False, marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0,
+                 frame_pad=None):
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
@@ -84,6 +93,24 @@ class MultiStreamDecoder:
                                 t.zeros((self.n_streams, 4), dtype=t.int32, device=decoder.device))
             self._emitted = 0                                         # bits the internal calls have emitted, per stream
             self._recent = np.zeros((self.n_streams, 0), dtype=np.uint8)    # the last bits-1 of them
+        self._frames = None
+        if frames:
+            if self._marker is None or not 8 <= int(period) or not 0 <= int(frame_drop_bits) < int(period) or self._marker[1] > int(period):
+                raise ValueError("frames=True needs marker=(value, bits), period=P >= max(8, bits) and 0 <= frame_drop_bits < P")
+            t, P, n = decoder.torch, int(period), self.n_streams
+            qb = (P - int(frame_drop_bits) + 7) // 8
+            pad = None
+            if frame_pad is not None:
+                pad = frame_pad if t.is_tensor(frame_pad) else t.from_numpy(np.frombuffer(bytes(frame_pad), dtype=np.uint8).copy())
+                pad = pad.to(device=decoder.device, dtype=t.uint8).reshape(-1).contiguous()
+                if pad.numel() < qb:
+                    raise ValueError(f"frame_pad must hold ceil((period - frame_drop_bits) / 8) = {qb} bytes")
+            self._frames = (int(frame_drop_bits), qb, pad)
+            # the unfinished frame of every stream, ping-ponged: a call reads one pair and writes the other
+            self._frame_carry = [(t.zeros((n, (P + 6) // 8), dtype=t.uint8, device=decoder.device),
+                                  t.zeros(n, dtype=t.int32, device=decoder.device)) for _ in range(2)]
+            self._frame_turn = 0
+            self._frames_done = [[] for _ in range(n)]                # (frames, marker_errors) per call, until taken
 
     @property
     def channel_errors(self):
@@ -124,6 +151,37 @@ class MultiStreamDecoder:
         self._recent = bits[:, max(bits.shape[1] - (m - 1), 0):]
         self._emitted += n_bits
 
+    def _extract(self, out, n_bits, phase0):
+        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted, bit 0 at phase phase0; the lock is that of the totals so far"""
+        value, m, P = self._marker
+        drop, qb, pad = self._frames
+        carry, carry_bits = self._frame_carry[self._frame_turn]
+        carry_out, carry_bits_out = self._frame_carry[1 - self._frame_turn]
+        frames, n, errors, _, _ = self.decoder.frames_extract(out, n_bits, P, phase0, self._marker_out[2], carry, carry_bits, value, m, drop,
+                                                              pad, out=self._frame_out(n_bits) + (carry_out, carry_bits_out))
+        self._frame_turn = 1 - self._frame_turn
+        n, frames, errors = n.cpu().numpy(), frames.cpu().numpy(), errors.cpu().numpy().view(np.uint32).astype(np.int64)
+        for i in range(self.n_streams):
+            if n[i]:
+                self._frames_done[i].append((frames[i, :n[i]].copy(), errors[i, :n[i]].copy()))
+
+    def _frame_out(self, n_bits):
+        t, dec = self.decoder.torch, self.decoder
+        cap = dec.frames_capacity(n_bits, self._marker[2])
+        return (t.empty((self.n_streams, cap, self._frames[1]), dtype=t.uint8, device=dec.device),
+                t.empty(self.n_streams, dtype=t.int32, device=dec.device), t.empty((self.n_streams, cap), dtype=t.int32, device=dec.device))
+
+    def take_frames(self) -> list:
+        """per stream (frames uint8 [n][ceil(Q/8)], marker_errors int64 [n]): the frames completed since the last take, in order"""
+        if self._frames is None:
+            raise AttributeError("this receiver was made without frames=True")
+        taken = []
+        for done in self._frames_done:
+            taken.append((np.concatenate([f for f, _ in done]) if done else np.zeros((0, self._frames[1]), dtype=np.uint8),
+                          np.concatenate([e for _, e in done]) if done else np.zeros(0, dtype=np.int64)))
+        self._frames_done = [[] for _ in range(self.n_streams)]
+        return taken
+
     def _append(self, symbols):
         if symbols is None:
             return
@@ -150,7 +208,10 @@ class MultiStreamDecoder:
         if self._totals is not None:
             self._count(out, n_bits, end)
         if self._marker is not None:
+            phase0 = self._emitted % self._marker[2]
             self._search(out, n_bits)
+            if self._frames is not None and n_bits:
+                self._extract(out, n_bits, phase0)
         self._first = False
         # whole bytes only: the rest waits in the carry, which the last call flushes
         bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
@@ -189,14 +250,18 @@ class MultiStreamDecoder:
 class StreamDecoder(MultiStreamDecoder):
     """MultiStreamDecoder for ONE long stream: push() and finish() take any tensor of whole trellis steps ([steps][R], flat, or a view
     that is not contiguous) and return `bytes`; `.channel_errors` (with channel_errors=True) is a pair of ints, `.marker_totals` (with
-    marker and period) a pair of [P] arrays and `.marker_lock` one (phase, inverted, errors, compared)."""
+    marker and period) a pair of [P] arrays and `.marker_lock` one (phase, inverted, errors, compared); take_frames() (with
+    frames=True) returns the one (frames, marker_errors) pair."""
 
     _RULE = "window, head, tail outside the argument rule of vit_hip_decode_stream"
     _SHAPE, _FINISHED, _EMPTY = "[steps][R]", "the stream is finished", "an empty stream"
 
     def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False,
-                 marker=None, period: int = None):
-        super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period)
+                 marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0, frame_pad=None):
+        super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period, frames, frame_drop_bits, frame_pad)
+
+    def take_frames(self):
+        return super().take_frames()[0]
 
     @property
     def marker_totals(self):
