@@ -53,6 +53,8 @@
  *   vit_hip_frames_extract    no reference counterpart: frame extraction -- the frames of the decoded bits cut at that lock, each on a
  *                             byte boundary, complemented, derandomised, the unfinished frame carried to the next call (rule below),
  *                             with vit_hip_frames_capacity
+ *   vit_hip_rs_create / vit_hip_rs_decode_batch  no reference counterpart: the outer Reed-Solomon code of a concatenated link --
+ *                             bounded-distance decoding over GF(256) of the interleaved codewords of those frames (rule below)
  *
  * Semantics are those of the reference SCALAR strategy (strict '>' decision, wrapping error_t arithmetic,
  * renormalise only when new_metric[0] >= threshold): SURVEY.md section 8(a').  All results are bit-exact.
@@ -682,6 +684,48 @@ int vit_hip_frames_extract(vit_hip_handle h, const uint8_t* d_bytes, size_t byte
                            size_t drop_bits, const uint8_t* d_pad, uint8_t* d_frames, size_t frame_stride_bytes, size_t max_frames,
                            uint32_t* d_n_frames, uint32_t* d_marker_errors, uint8_t* d_carry_out, uint32_t* d_carry_bits_out,
                            vit_hip_stream_t stream);
+
+/* ---- Reed-Solomon decoding: the outer code of a concatenated link, on the frames vit_hip_frames_extract wrote ---------------------
+ * A code over GF(256), described as libfec describes one:
+ *   gfpoly      the field polynomial with its x^8 term, primitive (0x187 CCSDS, 0x11D DVB); alpha = the element 0x02;
+ *   fcr, prim   the roots of the generator are alpha^(prim * (fcr + j)), 0 <= j < nroots; gcd(prim, 255) = 1, fcr <= 254;
+ *   nroots      2 .. 64 parity symbols; t = nroots div 2;
+ *   pad         virtual fill: n = 255 - pad symbols are transmitted, n > nroots;
+ *   dual_basis  0 / 1; 1 only with gfpoly 0x187.
+ * Rule, bit-exact and independent of the algorithm:
+ *   - codeword: bytes c_0 .. c_(n-1), c_0 the coefficient of x^(n-1) (first transmitted: data first, parity last); valid iff the
+ *     polynomial vanishes at all nroots roots;
+ *   - dual basis (CCSDS 131.0-B): the stored bytes are Berlekamp-representation symbols: conventional x is stored as the byte whose
+ *     bit 7-i is Tr(x * beta^i), beta = alpha^117, i = 0 .. 7.  The kernel maps stored to conventional on the way in and back on the
+ *     way out; Hamming distances are those of the stored bytes;
+ *   - interleave depth I >= 1: a frame is n * I bytes, symbol i of codeword c is frame byte i * I + c;
+ *   - decision: if a valid codeword v at Hamming distance e <= t of the received word exists it is unique: the output is v, the
+ *     status e.  Otherwise the output is the received word unchanged and the status -1.  The failure detection is complete.
+ * vit_hip_rs_create validates the parameters, builds the tables on the host and uploads them once to the handle's device;
+ * vit_hip_rs_destroy frees them (NULL is accepted).  These two are the only calls that allocate or copy.
+ * vit_hip_rs_decode_batch:
+ *   - input: the layout vit_hip_frames_extract writes: frame (r, f) at d_in + (r * max_frames + f) * frame_stride_bytes (0 => n * I; a
+ *     non-zero stride is at least that);
+ *   - d_n_frames [rows] on the device, or NULL: all max_frames frames of every row.  Frames f >= d_n_frames[r] are neither read nor
+ *     written, and neither are their status entries; a count above max_frames reads as max_frames;
+ *   - output: d_out == d_in (in place) or a buffer of the same layout that does not overlap it.  Out of place all n * I bytes of a
+ *     decoded frame are written; bytes behind them inside the stride are not;
+ *   - d_status: int32 [rows * max_frames * I], entry (r * max_frames + f) * I + c.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, code, d_in, d_out or d_status,
+ * a code made for another device, I = 0 or I > 2^24 - 1, a stride below n * I, d_out and d_in that overlap without being equal, more than 2^31 - 1
+ * blocks (rows * max_frames * ceil(I / 8)); at create for parameters outside the table above.  rows = 0 or max_frames = 0 returns
+ * VIT_HIP_OK with no work.
+ * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, synchronises nothing, can be
+ * captured into a hipGraph behind vit_hip_frames_extract, and reads the handle only for its device.
+ * Out of scope: erasure decoding; DVB-S's Forney (12 x 17) convolutional de-interleaver and its inverted every-eighth sync byte (the
+ * (204,188) code itself decodes its own packets here); a GPU Reed-Solomon encoder; symbol sizes other than 8 bits. */
+typedef struct vit_hip_rs_params { uint32_t gfpoly, fcr, prim, nroots, pad, dual_basis; } vit_hip_rs_params;
+typedef struct vit_hip_rs_code_s* vit_hip_rs_code;
+int vit_hip_rs_create(vit_hip_handle h, const vit_hip_rs_params* params, vit_hip_rs_code* out);
+void vit_hip_rs_destroy(vit_hip_rs_code code);
+int vit_hip_rs_decode_batch(vit_hip_handle h, vit_hip_rs_code code, const uint8_t* d_in, uint8_t* d_out, size_t frame_stride_bytes,
+                            size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t interleave, int32_t* d_status,
+                            vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

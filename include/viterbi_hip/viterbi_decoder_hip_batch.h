@@ -194,6 +194,23 @@ public:
                                      max_frames, d_n_frames, d_marker_errors, d_carry_out, d_carry_bits_out, stream),
               "vit_hip_frames_extract");
     }
+    // Reed-Solomon decoding (vit_hip_rs_create / vit_hip_rs_decode_batch): rs_create validates the code, builds its tables and uploads
+    // them once; the caller frees it with rs_destroy before this decoder goes.  rs_decode decodes the interleaved codewords of the frames
+    // frames_extract wrote -- frame (row, f) at d_in + (row * max_frames + f) * frame_stride_bytes (0: n * interleave), symbol i of codeword
+    // c at byte i * interleave + c -- in place (d_out == d_in) or into a buffer of the same layout; d_n_frames [rows] (nullptr: all
+    // max_frames) bounds the frames of a row that are touched; d_status [rows][max_frames][interleave] receives the byte errors corrected
+    // or -1 for a codeword left as received.
+    vit_hip_rs_code rs_create(const vit_hip_rs_params& params) {
+        vit_hip_rs_code code = nullptr;
+        check(vit_hip_rs_create(m_hip, &params, &code), "vit_hip_rs_create");
+        return code;
+    }
+    static void rs_destroy(vit_hip_rs_code code) { vit_hip_rs_destroy(code); }
+    void rs_decode(vit_hip_rs_code code, const uint8_t* d_in, uint8_t* d_out, size_t rows, size_t max_frames, const uint32_t* d_n_frames,
+                   size_t interleave, int32_t* d_status, size_t frame_stride_bytes = 0, void* stream = nullptr) {
+        check(vit_hip_rs_decode_batch(m_hip, code, d_in, d_out, frame_stride_bytes, rows, max_frames, d_n_frames, interleave, d_status, stream),
+              "vit_hip_rs_decode_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

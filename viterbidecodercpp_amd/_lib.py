@@ -36,6 +36,7 @@ EXPORTS = [
     "vit_hip_sync_build", "vit_hip_sync_search_workspace_bytes", "vit_hip_sync_search",
     "vit_hip_marker_search",
     "vit_hip_frames_capacity", "vit_hip_frames_extract",
+    "vit_hip_rs_create", "vit_hip_rs_destroy", "vit_hip_rs_decode_batch",
 ]
 
 
@@ -81,6 +82,12 @@ MARKER_ACCUMULATE = 1
 class VitHipSyncHypothesis(C.Structure):
     """vit_hip_sync_hypothesis: received symbols in front of a puncturing period, and the SYNC_* flags"""
     _fields_ = [("offset", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class VitHipRsParams(C.Structure):
+    """vit_hip_rs_params: a Reed-Solomon code over GF(256) as libfec describes one"""
+    _fields_ = [("gfpoly", C.c_uint32), ("fcr", C.c_uint32), ("prim", C.c_uint32), ("nroots", C.c_uint32), ("pad", C.c_uint32),
+                ("dual_basis", C.c_uint32)]
 
 
 class VitHipError(RuntimeError):
@@ -152,6 +159,10 @@ def load():
     L.vit_hip_frames_capacity.restype = sz
     L.vit_hip_frames_capacity.argtypes = [sz, sz]
     L.vit_hip_frames_extract.argtypes = [vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, sz, C.c_uint64, C.c_uint, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.vit_hip_rs_create.argtypes = [vp, C.POINTER(VitHipRsParams), C.POINTER(vp)]
+    L.vit_hip_rs_destroy.argtypes = [vp]
+    L.vit_hip_rs_destroy.restype = None
+    L.vit_hip_rs_decode_batch.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -15,6 +15,8 @@
 //                    (kernels_marker.hpp)
 //   vit_frames.hip   frame extraction: the frames of the caller's bytes cut at that lock, byte-aligned, with the carry between calls
 //                    (kernels_frames.hpp)
+//   vit_rs.hip       Reed-Solomon decoding of those frames' interleaved codewords: the code object with its tables (rs_tables.hpp)
+//                    and the decode (kernels_rs.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

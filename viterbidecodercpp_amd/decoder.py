@@ -293,6 +293,24 @@ class ViterbiDecoder_HIP:
         return rs + base.take_unreported_renormalisation()
 
 
+class _RsCode:
+    """a vit_hip_rs_code: the tables of one reed_solomon.RSCode on the device of a handle, which it keeps alive"""
+
+    def __init__(self, handle, code):
+        self._handle = handle
+        self._c = C.c_void_p()
+        params = _lib.VitHipRsParams(code.gfpoly, code.fcr, code.prim, code.nroots, code.pad, int(code.dual_basis))
+        _lib.check(_lib.load().vit_hip_rs_create(handle._h, C.byref(params), C.byref(self._c)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_c", None):
+                _lib.load().vit_hip_rs_destroy(self._c)
+                self._c = None
+        except Exception:
+            pass
+
+
 def _ptr(x):
     """the address a tensor starts at, as the C ABI takes it; NULL for None"""
     return None if x is None else C.c_void_p(x.data_ptr())
@@ -318,6 +336,7 @@ class BatchDecoder:
         self._soft_dtype = torch.int16 if self.soft_bytes == 2 else torch.int8
         self._error_dtype = torch.int16 if self.error_bytes == 2 else torch.uint8     # int16 carries the uint16 bit pattern
         self._ws = None
+        self._rs_codes = {}                     # RSCode -> _RsCode: a code's tables are uploaded once per decoder
 
     @property
     def plan(self) -> int:
@@ -903,6 +922,44 @@ class BatchDecoder:
             _ptr(carry_bits) if carry is not None else None, cstride, int(marker), marker_bits, drop_bits, _ptr(pad), _ptr(frames),
             int(frames.stride(1)), max_frames, _ptr(n_frames), _ptr(marker_errors), _ptr(carry_out), _ptr(carry_bits_out), self._stream()))
         return frames, n_frames, marker_errors, carry_out, carry_bits_out
+
+    def _rs_code(self, code):
+        """the vit_hip_rs_code of an RSCode: made at its first use, kept as long as this decoder"""
+        if code not in self._rs_codes:
+            self._rs_codes[code] = _RsCode(self._handle, code)
+        return self._rs_codes[code]
+
+    def rs_decode(self, code, frames, n_frames=None, interleave: int = 1, out=None, status=None):
+        """Reed-Solomon decoding (vit_hip_rs_decode_batch) of `frames`, the uint8 CUDA tensor [rows][max_frames][>= n * interleave]
+        frames_extract returns (or [max_frames][...]: one row; the last stride is the frame stride): `code` is a reed_solomon.RSCode,
+        symbol i of codeword c is frame byte i * interleave + c.  n_frames: the int32 CUDA tensor [rows] frames_extract returns -- frames
+        at or behind it are neither read nor written, and neither is their status -- or None: all of them.  out: None decodes in place,
+        or a tensor of the same shape and strides that does not overlap `frames`.  returns (frames, status): the tensor written and
+        int32 [rows][max_frames][interleave], the byte errors corrected in each codeword or -1 where more than t = nroots // 2 stand in
+        it (that codeword is left as received).  status = an int32 tensor of that size reuses it.  Nothing is copied to the host."""
+        t = self.torch
+        I = int(interleave)
+        if frames.dtype != t.uint8 or not frames.is_cuda or frames.dim() not in (2, 3) or (frames.numel() and frames.stride(-1) != 1):
+            raise ValueError("frames must be a uint8 CUDA tensor [rows][max_frames][>= n * interleave] or [max_frames][...]")
+        rows = 1 if frames.dim() == 2 else int(frames.shape[0])
+        max_frames = int(frames.shape[-2])
+        if I < 1 or frames.shape[-1] < code.n * I:
+            raise ValueError(f"a frame of {code.n} * {I} bytes does not fit the last dimension")
+        if frames.dim() == 3 and rows > 1 and max_frames > 0 and frames.stride(0) != max_frames * frames.stride(1):
+            raise ValueError("frames must be evenly spaced")
+        stride = int(frames.stride(-2)) if max_frames > 1 or rows > 1 else int(frames.shape[-1])
+        out = frames if out is None else out
+        if out is not frames and (out.dtype != t.uint8 or not out.is_cuda or out.shape != frames.shape or out.stride() != frames.stride()):
+            raise ValueError("out must be a uint8 CUDA tensor with the shape and strides of frames")
+        if n_frames is not None and (n_frames.dtype != t.int32 or not n_frames.is_cuda or not n_frames.is_contiguous() or n_frames.numel() != rows):
+            raise ValueError(f"n_frames must be a contiguous int32 CUDA tensor [{rows}]")
+        if status is None:
+            status = t.empty(tuple(frames.shape[:-1]) + (I,), dtype=t.int32, device=self.device)
+        elif status.dtype != t.int32 or not status.is_cuda or not status.is_contiguous() or status.numel() != rows * max_frames * I:
+            raise ValueError(f"status must be a contiguous int32 CUDA tensor of {rows} * {max_frames} * {I} entries")
+        _lib.check(_lib.load().vit_hip_rs_decode_batch(self._handle._h, self._rs_code(code)._c, _ptr(frames), _ptr(out), stride, rows, max_frames,
+                                                       _ptr(n_frames), I, _ptr(status), self._stream()))
+        return out, status
 
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The

@@ -53,7 +53,12 @@ class MultiStreamDecoder:
     ceil(Q/8) bytes for the Q = P - frame_drop_bits output bits: frame_sync.ccsds_randomizer).  The unfinished frame at the end of a
     call stays on the device in one of two carry buffers and is completed by a later call, however the pushes were cut.
     take_frames() returns, per stream, (uint8 [n][ceil(Q/8)], marker_errors int64 [n]) for the frames completed since the last
-    take; whether to trust a frame is the caller's decision, from its marker_errors.  Off (the default), nothing changes."""
+    take; whether to trust a frame is the caller's decision, from its marker_errors.  Off (the default), nothing changes.
+
+    rs=RSCode, rs_interleave=I (needs frames=True and (P - frame_drop_bits) / 8 == n * I): right behind every extraction the frames are
+    Reed-Solomon decoded in place on the device (BatchDecoder.rs_decode), and take_frames() returns (frames, marker_errors,
+    rs_status), rs_status int32 [n][I]: the byte errors corrected in each codeword, or -1 where it was left as received.  Without rs=
+    nothing changes, the 2-tuple included."""
 
     # how the errors word it; StreamDecoder has its own
     _RULE = "n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams"
@@ -61,7 +66,7 @@ class MultiStreamDecoder:
 
     def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
                  channel_errors: bool = False, marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0,
-                 frame_pad=None):
+                 frame_pad=None, rs=None, rs_interleave: int = 1):
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
@@ -110,7 +115,12 @@ class MultiStreamDecoder:
             self._frame_carry = [(t.zeros((n, (P + 6) // 8), dtype=t.uint8, device=decoder.device),
                                   t.zeros(n, dtype=t.int32, device=decoder.device)) for _ in range(2)]
             self._frame_turn = 0
-            self._frames_done = [[] for _ in range(n)]                # (frames, marker_errors) per call, until taken
+            self._frames_done = [[] for _ in range(n)]                # (frames, marker_errors[, rs_status]) per call, until taken
+        self._rs = None
+        if rs is not None:
+            if self._frames is None or int(rs_interleave) < 1 or (int(period) - int(frame_drop_bits)) != 8 * rs.n * int(rs_interleave):
+                raise ValueError("rs= needs frames=True and (period - frame_drop_bits) / 8 == rs.n * rs_interleave")
+            self._rs = (rs, int(rs_interleave))
 
     @property
     def channel_errors(self):
@@ -160,10 +170,15 @@ class MultiStreamDecoder:
         frames, n, errors, _, _ = self.decoder.frames_extract(out, n_bits, P, phase0, self._marker_out[2], carry, carry_bits, value, m, drop,
                                                               pad, out=self._frame_out(n_bits) + (carry_out, carry_bits_out))
         self._frame_turn = 1 - self._frame_turn
+        status = None
+        if self._rs is not None and frames.shape[1]:
+            _, status = self.decoder.rs_decode(self._rs[0], frames, n, self._rs[1])
+            status = status.cpu().numpy()
         n, frames, errors = n.cpu().numpy(), frames.cpu().numpy(), errors.cpu().numpy().view(np.uint32).astype(np.int64)
         for i in range(self.n_streams):
             if n[i]:
-                self._frames_done[i].append((frames[i, :n[i]].copy(), errors[i, :n[i]].copy()))
+                done = (frames[i, :n[i]].copy(), errors[i, :n[i]].copy())
+                self._frames_done[i].append(done if status is None else done + (status[i, :n[i]].copy(),))
 
     def _frame_out(self, n_bits):
         t, dec = self.decoder.torch, self.decoder
@@ -172,13 +187,16 @@ class MultiStreamDecoder:
                 t.empty(self.n_streams, dtype=t.int32, device=dec.device), t.empty((self.n_streams, cap), dtype=t.int32, device=dec.device))
 
     def take_frames(self) -> list:
-        """per stream (frames uint8 [n][ceil(Q/8)], marker_errors int64 [n]): the frames completed since the last take, in order"""
+        """per stream (frames uint8 [n][ceil(Q/8)], marker_errors int64 [n]) -- with rs= also rs_status int32 [n][I] --: the frames
+        completed since the last take, in order"""
         if self._frames is None:
             raise AttributeError("this receiver was made without frames=True")
+        empty = (np.zeros((0, self._frames[1]), dtype=np.uint8), np.zeros(0, dtype=np.int64))
+        if self._rs is not None:
+            empty += (np.zeros((0, self._rs[1]), dtype=np.int32),)
         taken = []
         for done in self._frames_done:
-            taken.append((np.concatenate([f for f, _ in done]) if done else np.zeros((0, self._frames[1]), dtype=np.uint8),
-                          np.concatenate([e for _, e in done]) if done else np.zeros(0, dtype=np.int64)))
+            taken.append(tuple(np.concatenate(part) for part in zip(*done)) if done else empty)
         self._frames_done = [[] for _ in range(self.n_streams)]
         return taken
 
@@ -251,14 +269,16 @@ class StreamDecoder(MultiStreamDecoder):
     """MultiStreamDecoder for ONE long stream: push() and finish() take any tensor of whole trellis steps ([steps][R], flat, or a view
     that is not contiguous) and return `bytes`; `.channel_errors` (with channel_errors=True) is a pair of ints, `.marker_totals` (with
     marker and period) a pair of [P] arrays and `.marker_lock` one (phase, inverted, errors, compared); take_frames() (with
-    frames=True) returns the one (frames, marker_errors) pair."""
+    frames=True) returns the one (frames, marker_errors) pair, or with rs= the one (frames, marker_errors, rs_status) triple."""
 
     _RULE = "window, head, tail outside the argument rule of vit_hip_decode_stream"
     _SHAPE, _FINISHED, _EMPTY = "[steps][R]", "the stream is finished", "an empty stream"
 
     def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False,
-                 marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0, frame_pad=None):
-        super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period, frames, frame_drop_bits, frame_pad)
+                 marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0, frame_pad=None, rs=None,
+                 rs_interleave: int = 1):
+        super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period, frames, frame_drop_bits, frame_pad, rs,
+                         rs_interleave)
 
     def take_frames(self):
         return super().take_frames()[0]
