@@ -19,6 +19,7 @@ CASES = {
     "ccsds": (("ccsds223dual", 5, 2, 5), 3, [4, 9]),
     "dvb": (("dvb", 1, 2, 5), 0, None),
     "short": (("short", 8, 1, 1), 5, None),
+    "deep": (("dvb", 11, 2, 5), 3, [4, 9]),                       # two tiles of codewords in every frame
 }
 
 

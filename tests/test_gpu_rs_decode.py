@@ -2,7 +2,9 @@
 buffers, written or not, and every status entry -- all stock codes in both bases, the nroots = 2, 3 and 64 codes and a shortened one,
 interleave depths 1, 2, 5, 8 and 11, batches 1x1, 3x2 and 2x5, 0 to 200 errors per codeword mixed inside a frame, a burst, the
 all-zero and all-0xFF words; in place and out of place, strides with guard bytes, frame counts of 0, a part and above max_frames;
-rejected arguments; frames_extract and rs_decode captured into one graph; the whole chain through StreamDecoder at 3 dB; and two streams at
+rejected arguments; a second pass over what those never reach -- all 16 primitive polynomials, nroots just above every power of two,
+k = 1 codes, every error count 0 .. t + 2, words whose first or last syndromes vanish, roots in the virtual fill, miscorrection at t = 2
+and 3, depths 9 .. 64 in several frames, frames of 3 bytes, the dword staging at every start, 70 000 blocks; frames_extract and rs_decode captured into one graph; the whole chain through StreamDecoder at 3 dB; and two streams at
 depth 5 through MultiStreamDecoder."""
 import ctypes as C
 import functools
@@ -87,6 +89,85 @@ def test_frames_at_or_past_the_count_and_their_status_are_not_written(shape, cou
     got, status, want, want_status = run(rs_cases.make_case(*shape), in_place, 3, counts)
     assert np.array_equal(status, want_status) and np.array_equal(got, want)
     assert (status == POISON32).any()
+
+
+# ---- the second pass: the cases of tests/rs_cases.py below SHAPES (tests/test_rs_cpu.py checks what each of them holds) -------------
+
+def equal(case, in_place, extra=0, counts=None, lead=0):
+    got, status, want, want_status = run(case, in_place, extra, counts, lead)
+    where = (case["I"], extra, counts, lead)
+    assert np.array_equal(status, want_status), (where, np.argwhere(status != want_status)[:8].tolist())
+    assert np.array_equal(got, want), (where, np.argwhere(got != want)[:8].tolist())
+    return status
+
+
+IN_PLACE = pytest.mark.parametrize("in_place", [True, False], ids=["inplace", "outofplace"])
+
+
+@IN_PLACE
+@pytest.mark.parametrize("name", rs_cases.SWEEPS)
+def test_every_error_count_from_none_to_two_beyond_t(name, in_place):
+    equal(rs_cases.make_sweep(name), in_place)
+
+
+@IN_PLACE
+@pytest.mark.parametrize("name,kinds", rs_cases.DESIGNED, ids=[d[0] for d in rs_cases.DESIGNED])
+def test_vanishing_syndromes_in_front_and_behind_and_roots_in_the_fill(name, kinds, in_place):
+    equal(rs_cases.make_designed(name, kinds), in_place)
+
+
+@IN_PLACE
+@pytest.mark.parametrize("name", rs_cases.MISCORRECTING)
+def test_words_beyond_t_move_to_the_codeword_within_t_where_there_is_one(name, in_place):
+    status = equal(rs_cases.make_miscorrecting(name), in_place)
+    assert (status >= 0).sum() >= 20 and (status == -1).sum() >= 20
+
+
+@IN_PLACE
+@pytest.mark.parametrize("shape", rs_cases.GEOMETRY, ids=lambda s: "-".join(map(str, s)))
+def test_every_polynomial_and_syndrome_geometry(shape, in_place):
+    equal(rs_cases.make_case(*shape), in_place)
+
+
+@IN_PLACE
+@pytest.mark.parametrize("shape", rs_cases.TILED, ids=lambda s: "-".join(map(str, s)))
+def test_several_tiles_and_several_frames(shape, in_place):
+    """interleave depths 9, 11, 16, 17 and 64: plain, strides with guard bytes at every misalignment, and frame counts"""
+    case = rs_cases.make_tiled(*shape)
+    equal(case, in_place)
+    for extra in (1, 7):
+        for lead in (1, 2, 3):
+            equal(case, in_place, extra, None, lead)
+    for counts in ([[0, 1, 7]] if case["rows"] == 3 else [[2, 0], [1, 5]]):
+        status = equal(case, in_place, 3, counts)
+        assert (status == POISON32).any() and (status != POISON32).any()
+
+
+@IN_PLACE
+@pytest.mark.parametrize("shape", rs_cases.TINY, ids=lambda s: "-".join(map(str, s)))
+def test_frames_shorter_than_the_way_to_the_next_dword(shape, in_place):
+    """3, 6 and 9 bytes a frame, starting at every residue of 4"""
+    case = rs_cases.make_case(*shape)
+    for extra in (0, 1, 2):
+        for lead in (0, 1, 2, 3):
+            equal(case, in_place, extra, None, lead)
+    equal(case, in_place, 1, [1, 0, 2], 3)
+
+
+@IN_PLACE
+@pytest.mark.parametrize("shape", rs_cases.DWORDS, ids=lambda s: "-".join(map(str, s)))
+def test_the_dword_staging_at_every_start_and_end(shape, in_place):
+    case = rs_cases.make_case(*shape)
+    for extra in (1, 2, 3):
+        for lead in (1, 2, 3):
+            equal(case, in_place, extra, None, lead)
+
+
+@IN_PLACE
+def test_seventy_thousand_blocks(in_place):
+    case = rs_cases.make_many()
+    assert case["rows"] * case["max_frames"] == 70000 and case["got"].size == 210000
+    equal(case, in_place)
 
 
 def test_rejections_launch_nothing():

@@ -48,6 +48,22 @@ inline const char* rs_params_invalid(const vit_hip_rs_params* p) {
     return nullptr;
 }
 
+// how the kernel cuts a codeword's 256-byte slot for the syndromes (kernels_rs.hpp): R2 lanes per segment, the power of two at or above
+// nroots; G = 64 / R2 segments of seg bytes, a multiple of 4; base = G * seg - n zero bytes in front.  nroots 2 .. 64, nroots < n <= 255
+struct RsGeometry {
+    uint32_t R2, G, seg, base;
+};
+
+inline RsGeometry rs_geometry(uint32_t nroots, uint32_t n) {
+    RsGeometry g{};
+    g.R2 = 2;
+    while (g.R2 < nroots) g.R2 *= 2;
+    g.G = 64 / g.R2;
+    g.seg = ((n + g.G - 1) / g.G + 3) / 4 * 4;                     // G * seg <= 256: 256 / G is a multiple of 4
+    g.base = g.G * g.seg - n;
+    return g;
+}
+
 // the blob of a code rs_params_invalid accepted
 inline void rs_build_tables(const vit_hip_rs_params* p, uint8_t* blob) {
     uint8_t* exp_t = blob + RS_EXP;

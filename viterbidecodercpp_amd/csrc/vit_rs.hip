@@ -81,11 +81,8 @@ int vit_hip_rs_decode_batch(vit_hip_handle h, vit_hip_rs_code code, const uint8_
     a.I = (uint32_t)interleave; a.tiles = (a.I + RS_TILE - 1) / RS_TILE;
     a.stride = frame_stride_bytes ? frame_stride_bytes : (uint64_t)a.n * a.I;
     a.max_frames = max_frames;
-    a.R2 = 2;
-    while (a.R2 < a.nroots) a.R2 *= 2;
-    a.G = 64 / a.R2;
-    a.seg = ((a.n + a.G - 1) / a.G + 3) / 4 * 4;                   // G * seg <= 256: 256 / G is a multiple of 4
-    a.base = a.G * a.seg - a.n;
+    const RsGeometry g = rs_geometry(a.nroots, a.n);
+    a.R2 = g.R2; a.G = g.G; a.seg = g.seg; a.base = g.base;
     VIT_HIP_ON_DEVICE(h->device);
     if (rs_launch_decode(a, (uint64_t)rows * max_frames, (hipStream_t)stream) != 0) return fail(VIT_HIP_ERR_RUNTIME, "rs decode launch failed");
     return VIT_HIP_OK;
