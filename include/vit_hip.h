@@ -631,7 +631,8 @@ int vit_hip_sync_search(vit_hip_handle h, const void* d_received, size_t n_recei
  * for its device.
  * Out of scope: an aperiodic "first hit under a threshold" search; markers longer than 64 bits; masked patterns such as DVB-S's
  * 0x47 x 7, 0xB8 as ONE pattern -- such a caller searches 0x47 at P = 1632, where the right phase has an error rate of about 1/8
- * against about 1/2 elsewhere, or at P = 13056. */
+ * against about 1/2 elsewhere, or at P = 13056; which packet of eight carries the 0xB8 is settled behind Reed-Solomon, by
+ * vit_hip_dvb_derandomize_batch. */
 #define VIT_HIP_MARKER_ACCUMULATE 1u  /* add to the totals in d_distance / d_count instead of overwriting them */
 typedef struct vit_hip_marker_lock { uint32_t phase, inverted, errors, compared; } vit_hip_marker_lock;
 int vit_hip_marker_search(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_row_stride, size_t rows, size_t n_bits,
@@ -676,7 +677,8 @@ int vit_hip_marker_search(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes
  * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, synchronises nothing, can be
  * captured into a hipGraph, and reads the handle only for its device.
  * Out of scope: a lock threshold or flywheel policy (the caller decides from d_marker_errors whether to trust a frame); frames of
- * varying length; DVB-S's inverted every-eighth sync byte as part of extraction. */
+ * varying length; DVB-S's inverted every-eighth sync byte as part of extraction (vit_hip_dvb_derandomize_batch puts it upright, behind
+ * vit_hip_deinterleave_batch and vit_hip_rs_decode_batch). */
 size_t vit_hip_frames_capacity(size_t n_bits, size_t period_bits);   /* ceil(n_bits / period_bits); 0 for period_bits = 0 */
 int vit_hip_frames_extract(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_row_stride, size_t rows, size_t n_bits,
                            size_t period_bits, size_t phase0, const vit_hip_marker_lock* d_lock, const uint8_t* d_carry_in,
@@ -717,8 +719,9 @@ int vit_hip_frames_extract(vit_hip_handle h, const uint8_t* d_bytes, size_t byte
  * VIT_HIP_OK with no work.
  * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, synchronises nothing, can be
  * captured into a hipGraph behind vit_hip_frames_extract, and reads the handle only for its device.
- * Out of scope: erasure decoding; DVB-S's Forney (12 x 17) convolutional de-interleaver and its inverted every-eighth sync byte (the
- * (204,188) code itself decodes its own packets here); a GPU Reed-Solomon encoder; symbol sizes other than 8 bits. */
+ * Out of scope: erasure decoding; a GPU Reed-Solomon encoder; symbol sizes other than 8 bits.  DVB-S's Forney (12 x 17) convolutional
+ * de-interleaver and its inverted every-eighth sync byte are calls of their own on either side of this one (below): the (204,188)
+ * code decodes the packets vit_hip_deinterleave_batch wrote. */
 typedef struct vit_hip_rs_params { uint32_t gfpoly, fcr, prim, nroots, pad, dual_basis; } vit_hip_rs_params;
 typedef struct vit_hip_rs_code_s* vit_hip_rs_code;
 int vit_hip_rs_create(vit_hip_handle h, const vit_hip_rs_params* params, vit_hip_rs_code* out);
@@ -726,6 +729,67 @@ void vit_hip_rs_destroy(vit_hip_rs_code code);
 int vit_hip_rs_decode_batch(vit_hip_handle h, vit_hip_rs_code code, const uint8_t* d_in, uint8_t* d_out, size_t frame_stride_bytes,
                             size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t interleave, int32_t* d_status,
                             vit_hip_stream_t stream);
+
+/* ---- the DVB-S outer chain: convolutional de-interleaver in front of Reed-Solomon, energy-dispersal removal behind it -------------
+ * Behind the inner code a DVB-S stream is convolutionally (Forney) interleaved: the 204 bytes vit_hip_frames_extract cuts at the sync
+ * byte are not a codeword until vit_hip_deinterleave_batch has put every byte back, and behind vit_hip_rs_decode_batch the 187
+ * payload bytes still carry the energy-dispersal sequence, which restarts every eighth packet (a fixed pad cannot remove it) where
+ * the sync byte is inverted: vit_hip_dvb_derandomize_batch.
+ *
+ * vit_hip_deinterleave_batch: branches = B >= 2, cell = M >= 1 bytes per delay unit, packet_bytes = n, a multiple of B (DVB-S: 12, 17,
+ * 204).  Byte i of every packet rides branch i mod B -- the sync byte branch 0 --, D = (B-1) M B is the longest delay in bytes, H =
+ * ceil(D / n) the packets of history (DVB-S: 2244 and 11).  (H + 1) n <= 32768 is required: a block stages H packets and its own in
+ * LDS.  Rule, bit-exact, per row r:
+ *   - input: packet (r, f) at d_in + (r * max_frames + f) * frame_stride_bytes (0 => n; a non-zero stride is at least n), the layout
+ *     vit_hip_frames_extract writes.  nf = min(d_n_frames[r], max_frames); d_n_frames == NULL: all max_frames packets;
+ *   - history: row r of d_hist_in starts at r * hist_row_stride (0 => H n; a non-zero stride is at least that; in and out alike) and
+ *     holds H packets packed, the newest last, of which the last fill = min(d_fill_in[r], H) are real.  d_hist_in == NULL: every
+ *     fill = 0, and d_fill_in is not read.  The logical sequence S is the fill real history packets, then the nf input packets; T =
+ *     fill + nf; Sb is its byte stream;
+ *   - output: nout = max(0, T - H), written to d_n_out[r].  Byte i of output packet k < nout is Sb[(H + k) n + i - (B-1 - i mod B) M B]
+ *     (T - nout = H whenever nout > 0: the index is never negative), at d_out + (r * max_frames + k) * out_stride_bytes (0 => n).
+ *     Bytes behind n inside a stride and packets k >= nout are NOT written; the output is compacted from packet 0, so
+ *     vit_hip_rs_decode_batch(d_out, d_n_out, interleave = 1) takes it as it stands;
+ *   - new history: the last min(H, T) packets of S, right-aligned in row r of d_hist_out; d_fill_out[r] = min(H, T).  The bytes of the
+ *     row in front of them are not written.  In and out are distinct buffers that overlap neither each other nor the input (the caller
+ *     ping-pongs them, as the carry of vit_hip_frames_extract), d_out overlaps neither the input nor either history, and the count
+ *     arrays written (d_n_out, d_fill_out) overlap neither each other nor those read.
+ * Whatever the count and fill memory holds, the kernel stays inside its buffers.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_in, d_out, d_n_out, d_hist_out
+ * or d_fill_out, d_hist_in without d_fill_in, B < 2, M < 1, n not a multiple of B, (H + 1) n > 32768, a stride that is too small,
+ * buffers that overlap as said above, more than 2^31 - 1 rows, packets per row or blocks.  rows = 0 or max_frames = 0 returns
+ * VIT_HIP_OK with no work.
+ *
+ * vit_hip_dvb_derandomize_batch: the sequence is that of EN 300 421: 1 + x^14 + x^15, registers 1 .. 15 loaded with 100101010000000,
+ * the output reg 14 ^ reg 15 fed back into register 1, bits MSB-first into prbs[0 .. 1502] = 03 F6 08 34 30 B8 A3 93 ... CB; it starts
+ * behind the inverted sync byte and runs, its output gated, across the seven upright ones.  Rule per row r:
+ *   - input: packets in the layout above with packet_bytes >= 188 (0 stride => packet_bytes), of which only the first 188 bytes are
+ *     read (204: the parity stays behind); nf as above;
+ *   - group phase: d_phase_in[r] = g in 0 .. 7 is the place of packet 0 of this call in its group of eight; any value >= 8 means
+ *     unknown, d_phase_in == NULL all unknown.  An unknown phase is voted from this call's sync bytes: cost(g) = sum over f < nf of
+ *     popcount(in[f][0] ^ E(g, f)), E = 0xB8 if (g + f) mod 8 = 0, else 0x47; the lowest cost wins, the lower g on a tie; with nf = 0
+ *     it stays unknown.  d_phase_out[r] = (g + nf) mod 8, or 0xFFFFFFFF while unknown (a known g with nf = 0 comes back as it went in);
+ *   - output packet f < nf, 188 bytes at d_out + (r * max_frames + f) * out_stride_bytes (0 => 188), with q = (g + f) mod 8: byte 0 =
+ *     in[0] ^ 0xFF if q = 0, else in[0] (de-inverted, not forced); byte i, 1 <= i <= 187, = in[i] ^ prbs[188 q + i - 1];
+ *     d_sync_errors[r * max_frames + f] (uint32, may be NULL) = popcount(in[0] ^ E(g, f)); where d_rs_status[r * max_frames + f] (int32,
+ *     may be NULL: the status vit_hip_rs_decode_batch wrote at interleave 1) is negative, bit 7 of output byte 1 -- the MPEG
+ *     transport_error_indicator -- is set.  Packets f >= nf (and their sync errors) and bytes behind 188 inside a stride are NOT written;
+ *   - d_out == d_in with equal strides is in place (one workgroup per row: an unknown phase reads every sync byte before one is
+ *     rewritten; the fast way is out of place); otherwise the two do not overlap.  d_phase_out does not overlap d_phase_in.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_in, d_out or d_phase_out,
+ * packet_bytes < 188, a stride that is too small, d_out overlapping d_in otherwise than above, overlapping phase arrays, more than
+ * 2^31 - 1 rows, packets per row or blocks.  rows = 0 or max_frames = 0 returns VIT_HIP_OK with no work.
+ * Batch calls like the others: each only enqueues ONE kernel on `stream` (no memset), allocates nothing, synchronises nothing, can be
+ * captured into a hipGraph around vit_hip_rs_decode_batch, and reads the handle only for its device.
+ * Out of scope: code rates other than through the existing depuncturing front end; DVB-S2; erasures handed to the outer code. */
+int vit_hip_deinterleave_batch(vit_hip_handle h, const uint8_t* d_in, size_t frame_stride_bytes, size_t rows, size_t max_frames,
+                               const uint32_t* d_n_frames, size_t branches, size_t cell, size_t packet_bytes, const uint8_t* d_hist_in,
+                               const uint32_t* d_fill_in, size_t hist_row_stride, uint8_t* d_out, size_t out_stride_bytes,
+                               uint32_t* d_n_out, uint8_t* d_hist_out, uint32_t* d_fill_out, vit_hip_stream_t stream);
+int vit_hip_dvb_derandomize_batch(vit_hip_handle h, const uint8_t* d_in, size_t frame_stride_bytes, size_t packet_bytes, size_t rows,
+                                  size_t max_frames, const uint32_t* d_n_frames, const uint32_t* d_phase_in, const int32_t* d_rs_status,
+                                  uint8_t* d_out, size_t out_stride_bytes, uint32_t* d_phase_out, uint32_t* d_sync_errors,
+                                  vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

@@ -211,6 +211,30 @@ public:
         check(vit_hip_rs_decode_batch(m_hip, code, d_in, d_out, frame_stride_bytes, rows, max_frames, d_n_frames, interleave, d_status, stream),
               "vit_hip_rs_decode_batch");
     }
+    // The DVB-S stages on either side of rs_decode (vit_hip_deinterleave_batch / vit_hip_dvb_derandomize_batch).  deinterleave undoes the
+    // convolutional interleaver (DVB-S: branches 12, cell 17, packet_bytes 204) on the packets frames_extract wrote: d_hist_in / d_fill_in
+    // (nullptr: none) are the H = ceil((branches-1) * cell * branches / packet_bytes) packets the previous call left as d_hist_out /
+    // d_fill_out, d_out / d_n_out [rows] receive the packets completed, compacted from packet 0 of every row, as rs_decode(interleave 1)
+    // takes them.  dvb_derandomize XORs the energy-dispersal sequence off the first 188 bytes of every packet and puts the inverted
+    // every-eighth sync byte upright; d_phase_in [rows] (nullptr or a value >= 8: voted from the sync bytes) is the place of packet 0 in its
+    // group of eight, d_phase_out [rows] that of the next call's; d_rs_status [rows][max_frames] (may be nullptr) sets the
+    // transport_error_indicator where negative, d_sync_errors [rows][max_frames] (may be nullptr) receives the sync byte's bit errors.
+    void deinterleave(const uint8_t* d_in, size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t branches, size_t cell,
+                      size_t packet_bytes, const uint8_t* d_hist_in, const uint32_t* d_fill_in, uint8_t* d_out, uint32_t* d_n_out,
+                      uint8_t* d_hist_out, uint32_t* d_fill_out, size_t frame_stride_bytes = 0, size_t out_stride_bytes = 0,
+                      size_t hist_row_stride = 0, void* stream = nullptr) {
+        check(vit_hip_deinterleave_batch(m_hip, d_in, frame_stride_bytes, rows, max_frames, d_n_frames, branches, cell, packet_bytes, d_hist_in,
+                                         d_fill_in, hist_row_stride, d_out, out_stride_bytes, d_n_out, d_hist_out, d_fill_out, stream),
+              "vit_hip_deinterleave_batch");
+    }
+    void dvb_derandomize(const uint8_t* d_in, size_t packet_bytes, size_t rows, size_t max_frames, const uint32_t* d_n_frames,
+                         const uint32_t* d_phase_in, uint8_t* d_out, uint32_t* d_phase_out, const int32_t* d_rs_status = nullptr,
+                         uint32_t* d_sync_errors = nullptr, size_t frame_stride_bytes = 0, size_t out_stride_bytes = 0,
+                         void* stream = nullptr) {
+        check(vit_hip_dvb_derandomize_batch(m_hip, d_in, frame_stride_bytes, packet_bytes, rows, max_frames, d_n_frames, d_phase_in, d_rs_status,
+                                            d_out, out_stride_bytes, d_phase_out, d_sync_errors, stream),
+              "vit_hip_dvb_derandomize_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -11,8 +11,11 @@ from .sync import enumerate_hypotheses  # noqa: F401
 from .frame_sync import CCSDS_ASM, DVB_SYNC, ccsds_randomizer, frames_extract_numpy, marker_lock_numpy, marker_search_numpy  # noqa: F401
 from .reed_solomon import (CCSDS_RS_255_223, CCSDS_RS_255_223_DUAL, CCSDS_RS_255_239, CCSDS_RS_255_239_DUAL, DVB_RS_204_188, RSCode,  # noqa: F401
                            rs_decode_numpy, rs_encode_numpy)
-from . import _lib, dist, frame_sync, reed_solomon, sync, synth  # noqa: F401
+from .dvb import (DVB_INTERLEAVER, conv_deinterleave_numpy, conv_interleave_numpy, dvb_derandomize_numpy, dvb_prbs,  # noqa: F401
+                  dvb_randomize_numpy)
+from . import _lib, dist, dvb, frame_sync, reed_solomon, sync, synth  # noqa: F401
 
-__all__ = ["CCSDS_RS_255_223", "CCSDS_RS_255_223_DUAL", "CCSDS_RS_255_239", "CCSDS_RS_255_239_DUAL", "DVB_RS_204_188", "RSCode",
+__all__ = ["DVB_INTERLEAVER", "conv_deinterleave_numpy", "conv_interleave_numpy", "dvb_derandomize_numpy", "dvb_prbs", "dvb_randomize_numpy",
+           "CCSDS_RS_255_223", "CCSDS_RS_255_223_DUAL", "CCSDS_RS_255_239", "CCSDS_RS_255_239_DUAL", "DVB_RS_204_188", "RSCode",
            "rs_decode_numpy", "rs_encode_numpy", "CCSDS_ASM", "DVB_SYNC", "ccsds_randomizer", "frames_extract_numpy", "marker_lock_numpy", "marker_search_numpy", "COMMON_CODES", "Code", "DecoderConfig", "get_decoding_config", "SOFT16", "SOFT8", "HARD8", "BatchDecoder", "DecodePipeline",
            "MultiStreamDecoder", "StreamDecoder", "ViterbiBranchTable", "ViterbiDecoder_Config", "ViterbiDecoder_Core", "ViterbiDecoder_HIP", "enumerate_hypotheses", "pack_blob"]

@@ -17,6 +17,8 @@
 //                    (kernels_frames.hpp)
 //   vit_rs.hip       Reed-Solomon decoding of those frames' interleaved codewords: the code object with its tables (rs_tables.hpp)
 //                    and the decode (kernels_rs.hpp)
+//   vit_dvb.hip      the DVB-S stages on either side of it: the convolutional de-interleaver and the energy-dispersal removal
+//                    (kernels_dvb.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,8 +3,8 @@
 // interleaved codewords of frames in the layout vit_hip_frames_extract writes).  It works on the caller's bytes alone and reads the
 // handle only for its device.  The kernel of kernels_rs.hpp is launched only here.  Host-side logic only: argument checking, the
 // tables and the launch.
-// Out of scope: erasure decoding; DVB-S's Forney (12 x 17) convolutional de-interleaver and its inverted every-eighth sync byte; a GPU
-// Reed-Solomon encoder; symbol sizes other than 8 bits.
+// Out of scope: erasure decoding; a GPU Reed-Solomon encoder; symbol sizes other than 8 bits.  DVB-S's Forney (12 x 17) convolutional
+// de-interleaver and its inverted every-eighth sync byte live in vit_dvb.hip.
 #include "vit_internal.hpp"
 #include "kernels_rs.hpp"
 

@@ -961,6 +961,97 @@ class BatchDecoder:
                                                        _ptr(n_frames), I, _ptr(status), self._stream()))
         return out, status
 
+    def _packets(self, x, what, least):
+        """(rows, max_frames, packet stride) of a uint8 CUDA tensor [rows][max_frames][>= least] or [max_frames][...] with evenly spaced packets"""
+        t = self.torch
+        if x.dtype != t.uint8 or not x.is_cuda or x.dim() not in (2, 3) or (x.numel() and x.stride(-1) != 1) or x.shape[-1] < least:
+            raise ValueError(f"{what} must be a uint8 CUDA tensor [rows][max_frames][>= {least}] or [max_frames][...]")
+        rows, mf = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2])
+        if x.dim() == 3 and rows > 1 and mf > 0 and x.stride(0) != mf * x.stride(1):
+            raise ValueError(f"{what} must be evenly spaced")
+        return rows, mf, (int(x.stride(-2)) if mf > 1 or rows > 1 else int(x.shape[-1]))
+
+    def _counts(self, x, rows, what):
+        t = self.torch
+        if x is not None and (x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != rows):
+            raise ValueError(f"{what} must be a contiguous int32 CUDA tensor [{rows}]")
+        return x
+
+    def deinterleave(self, packets, n_frames=None, branches: int = 12, cell: int = 17, hist=None, fill=None, packet_bytes: int = None,
+                     out=None):
+        """the convolutional (Forney) de-interleaver (vit_hip_deinterleave_batch; dvb.DVB_INTERLEAVER = (12, 17)) on `packets`, the
+        uint8 CUDA tensor [rows][max_frames][>= n] frames_extract returns (or [max_frames][...]: one row; n = packet_bytes, by default
+        the last dimension, a multiple of branches).  n_frames: the int32 CUDA tensor [rows] frames_extract returns, or None: all.
+        hist / fill: the uint8 [rows][H n] and int32 [rows] the previous call returned as hist_out / fill_out (None: nothing carried), H
+        = ceil((branches-1) cell branches / n).  returns (out, n_out, hist_out, fill_out): uint8 of the shape of `packets` of which the
+        first n_out[r] (int32 [rows]) packets of row r are written -- byte i of packet k is stream byte (H + k) n + i - (branches-1 - i
+        mod branches) cell branches of the real history packets followed by the input --, as rs_decode(interleave=1) takes them, and the
+        last min(H, all) packets of that stream with their number.  out = the same four reuses those tensors; hist and hist_out must be
+        distinct and have the same row stride.  Nothing is copied to the host."""
+        t = self.torch
+        B, M = int(branches), int(cell)
+        n = int(packets.shape[-1]) if packet_bytes is None else int(packet_bytes)
+        rows, mf, stride = self._packets(packets, "packets", n)
+        if B < 2 or M < 1 or n < 1 or n % B:
+            raise ValueError("branches must be at least 2, cell at least 1, packet_bytes a multiple of branches")
+        H = -(-(B - 1) * M * B // n)
+        if out is None:
+            out = (t.empty(tuple(packets.shape[:-1]) + (n,), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device),
+                   t.empty((rows, H * n), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device))
+        d_out, n_out, hist_out, fill_out = out
+        orows, omf, ostride = self._packets(d_out, "out[0]", n)
+        if (orows, omf) != (rows, mf):
+            raise ValueError(f"out[0] must hold [{rows}][{mf}] packets")
+        self._counts(n_frames, rows, "n_frames"), self._counts(n_out, rows, "out[1]"), self._counts(fill_out, rows, "out[3]")
+        for x in (hist_out, hist):
+            if x is not None and (x.dtype != t.uint8 or not x.is_cuda or x.dim() != 2 or x.shape[0] != rows or x.shape[1] < H * n or x.stride(1) != 1):
+                raise ValueError(f"a history must be a uint8 CUDA tensor [{rows}][>= {H * n}] with contiguous rows")
+        hstride = int(hist_out.stride(0)) if rows > 1 else int(hist_out.shape[1])
+        if hist is not None:
+            if self._counts(fill, rows, "fill") is None:
+                raise ValueError("hist needs fill")
+            if (int(hist.stride(0)) if rows > 1 else int(hist.shape[1])) != hstride or hist.data_ptr() == hist_out.data_ptr():
+                raise ValueError("hist and hist_out must be distinct tensors with the same row stride")
+        _lib.check(_lib.load().vit_hip_deinterleave_batch(
+            self._handle._h, _ptr(packets), stride, rows, mf, _ptr(n_frames), B, M, n, _ptr(hist), _ptr(fill) if hist is not None else None,
+            hstride, _ptr(d_out), ostride, _ptr(n_out), _ptr(hist_out), _ptr(fill_out), self._stream()))
+        return d_out, n_out, hist_out, fill_out
+
+    def dvb_derandomize(self, packets, n_frames=None, phase=None, rs_status=None, out=None, phase_out=None, sync_errors=None,
+                        in_place: bool = False):
+        """DVB-S energy-dispersal removal (vit_hip_dvb_derandomize_batch) on `packets`, uint8 CUDA [rows][max_frames][>= 188] (or
+        [max_frames][...]: one row), of which the first 188 bytes of each are read -- 204-byte packets as rs_decode left them are fine.
+        n_frames: int32 CUDA [rows] or None: all.  phase: int32 CUDA [rows], the place 0 .. 7 of packet 0 in its group of eight; a
+        value outside (-1, say) or None means unknown: voted from this call's sync bytes.  rs_status: the int32 [rows][max_frames][1]
+        rs_decode returned, or None: where negative, the packet's transport_error_indicator is set.  returns (out, phase_out,
+        sync_errors): uint8 [rows][max_frames][188] of which the packets below n_frames are written -- byte 0 de-inverted at the head of
+        a group, bytes 1 .. 187 XORed with dvb.dvb_prbs() --, int32 [rows] = the phase of the next call's packet 0 (-1 while unknown: a
+        row without packets), int32 [rows][max_frames] = the bits the sync byte differs in from 0x47 (0xB8 at the head of a group).
+        out / phase_out / sync_errors reuse tensors; in_place=True writes into `packets` (one workgroup per row: slower on long rows).
+        Nothing is copied to the host."""
+        t = self.torch
+        rows, mf, stride = self._packets(packets, "packets", 188)
+        if in_place:
+            if out is not None:
+                raise ValueError("in_place=True writes into packets: no out")
+            d_out, ostride = packets, stride
+        else:
+            d_out = t.empty(tuple(packets.shape[:-1]) + (188,), dtype=t.uint8, device=self.device) if out is None else out
+            orows, omf, ostride = self._packets(d_out, "out", 188)
+            if (orows, omf) != (rows, mf):
+                raise ValueError(f"out must hold [{rows}][{mf}] packets")
+        self._counts(n_frames, rows, "n_frames"), self._counts(phase, rows, "phase")
+        phase_out = t.empty(rows, dtype=t.int32, device=self.device) if phase_out is None else self._counts(phase_out, rows, "phase_out")
+        if sync_errors is None:
+            sync_errors = t.empty(tuple(packets.shape[:-1]), dtype=t.int32, device=self.device)
+        for x, what in ((sync_errors, "sync_errors"), (rs_status, "rs_status")):
+            if x is not None and (x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != rows * mf):
+                raise ValueError(f"{what} must be a contiguous int32 CUDA tensor of {rows} * {mf} entries")
+        _lib.check(_lib.load().vit_hip_dvb_derandomize_batch(
+            self._handle._h, _ptr(packets), stride, int(packets.shape[-1]), rows, mf, _ptr(n_frames), _ptr(phase), _ptr(rs_status), _ptr(d_out),
+            ostride, _ptr(phase_out), _ptr(sync_errors), self._stream()))
+        return d_out, phase_out, sync_errors
+
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The
         workspace is an array of independent slabs of `workspace_tile_frames` frames (vit_hip_info), so `frames` frames

@@ -58,7 +58,16 @@ class MultiStreamDecoder:
     rs=RSCode, rs_interleave=I (needs frames=True and (P - frame_drop_bits) / 8 == n * I): right behind every extraction the frames are
     Reed-Solomon decoded in place on the device (BatchDecoder.rs_decode), and take_frames() returns (frames, marker_errors,
     rs_status), rs_status int32 [n][I]: the byte errors corrected in each codeword, or -1 where it was left as received.  Without rs=
-    nothing changes, the 2-tuple included."""
+    nothing changes, the 2-tuple included.
+
+    deinterleave=(B, M) (dvb.DVB_INTERLEAVER; needs frames=True, frame_drop_bits=0, no frame_pad and P = 8 n with n a multiple of B; with
+    rs= also rs_interleave=1 and rs.n == n): the frames are the n-byte packets of a convolutionally interleaved stream, the sync byte in
+    front.  Every internal call runs extract -> BatchDecoder.deinterleave -> rs_decode in place -> (dvb_derandomize=True, n >= 188:)
+    BatchDecoder.dvb_derandomize on the device; the de-interleaver's history and fill and the group phase stay there in ping-ponged
+    buffers.  When a stream's (phase, inverted) lock differs from the one the call before extracted at, its fill and group phase are
+    reset on the device (a torch.where on the lock tensors: no read-back), so the packets of the old alignment never meet those of the
+    new one; the first H = ceil((B-1) M B / n) packets behind every (re-)lock fill the delay lines and give no output.  take_frames()
+    then returns per stream (packets, errors[, rs_status]) -- see there.  Without the two keywords nothing changes."""
 
     # how the errors word it; StreamDecoder has its own
     _RULE = "n_streams, window, head, tail outside the argument rule of vit_hip_decode_streams"
@@ -66,7 +75,7 @@ class MultiStreamDecoder:
 
     def __init__(self, decoder: BatchDecoder, n_streams: int, window: int = None, head: int = None, tail: int = None,
                  channel_errors: bool = False, marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0,
-                 frame_pad=None, rs=None, rs_interleave: int = 1):
+                 frame_pad=None, rs=None, rs_interleave: int = 1, deinterleave=None, dvb_derandomize: bool = False):
         self.decoder = decoder
         self.n_streams = int(n_streams)
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
@@ -121,6 +130,27 @@ class MultiStreamDecoder:
             if self._frames is None or int(rs_interleave) < 1 or (int(period) - int(frame_drop_bits)) != 8 * rs.n * int(rs_interleave):
                 raise ValueError("rs= needs frames=True and (period - frame_drop_bits) / 8 == rs.n * rs_interleave")
             self._rs = (rs, int(rs_interleave))
+        self._dvb = None
+        if deinterleave is not None:
+            B, M = int(deinterleave[0]), int(deinterleave[1])
+            if (self._frames is None or int(frame_drop_bits) != 0 or frame_pad is not None or int(period) % 8 or B < 2 or M < 1
+                    or (int(period) // 8) % B or (self._rs is not None and self._rs[1] != 1)):
+                raise ValueError("deinterleave=(B, M) needs frames=True, frame_drop_bits=0, no frame_pad, period = 8 n with n a multiple of B, "
+                                 "and with rs= rs_interleave=1 and rs.n == n")
+            t, nb, n = decoder.torch, int(period) // 8, self.n_streams
+            H = -(-(B - 1) * M * B // nb)
+            if (H + 1) * nb > 32768:
+                raise ValueError("deinterleave=(B, M): (H + 1) * n is above 32768 (vit_hip_deinterleave_batch)")
+            if dvb_derandomize and nb < 188:
+                raise ValueError("dvb_derandomize=True needs packets of at least 188 bytes")
+            self._dvb = (B, M, bool(dvb_derandomize), nb)
+            # history, fill and group phase of every stream, ping-ponged; the (phase, inverted) the last extraction cut at
+            self._dvb_state = [(t.zeros((n, H * nb), dtype=t.uint8, device=decoder.device), t.zeros(n, dtype=t.int32, device=decoder.device),
+                                t.full((n,), -1, dtype=t.int32, device=decoder.device)) for _ in range(2)]
+            self._dvb_turn = 0
+            self._dvb_lock = t.zeros((n, 2), dtype=t.int32, device=decoder.device)
+        elif dvb_derandomize:
+            raise ValueError("dvb_derandomize=True needs deinterleave=(B, M)")
 
     @property
     def channel_errors(self):
@@ -170,15 +200,42 @@ class MultiStreamDecoder:
         frames, n, errors, _, _ = self.decoder.frames_extract(out, n_bits, P, phase0, self._marker_out[2], carry, carry_bits, value, m, drop,
                                                               pad, out=self._frame_out(n_bits) + (carry_out, carry_bits_out))
         self._frame_turn = 1 - self._frame_turn
-        status = None
-        if self._rs is not None and frames.shape[1]:
+        status, n_errors = None, n                                # `errors` holds one entry per frame extracted ...
+        if self._dvb is not None:
+            frames, n, errors, status = self._dvb_chain(frames, n, errors)
+            if self._dvb[2]:
+                n_errors = n                                      # ... or, derandomised, one per packet that came out
+        elif self._rs is not None and frames.shape[1]:
             _, status = self.decoder.rs_decode(self._rs[0], frames, n, self._rs[1])
-            status = status.cpu().numpy()
+        status = None if status is None else status.cpu().numpy()
+        n_errors = n_errors.cpu().numpy()
         n, frames, errors = n.cpu().numpy(), frames.cpu().numpy(), errors.cpu().numpy().view(np.uint32).astype(np.int64)
         for i in range(self.n_streams):
-            if n[i]:
-                done = (frames[i, :n[i]].copy(), errors[i, :n[i]].copy())
+            if n[i] or n_errors[i]:
+                done = (frames[i, :n[i]].copy(), errors[i, :n_errors[i]].copy())
                 self._frames_done[i].append(done if status is None else done + (status[i, :n[i]].copy(),))
+
+    def _dvb_chain(self, frames, n, errors):
+        """the packets one extraction wrote -> de-interleaved, Reed-Solomon decoded in place, derandomised: (packets, their number per
+        stream, sync_errors -- or the marker_errors as they came --, rs_status or None), all on the device"""
+        t, dec = self.decoder.torch, self.decoder
+        B, M, derandomize, nb = self._dvb
+        lock = self._marker_out[2][:, :2]
+        changed = (lock != self._dvb_lock).any(dim=1)
+        self._dvb_lock = lock.clone()
+        hist, fill, phase = self._dvb_state[self._dvb_turn]
+        hist_out, fill_out, phase_out = self._dvb_state[1 - self._dvb_turn]
+        self._dvb_turn = 1 - self._dvb_turn
+        fill = t.where(changed, t.zeros_like(fill), fill)
+        phase = t.where(changed, t.full_like(phase, -1), phase)
+        out, n_out, _, _ = dec.deinterleave(frames, n, B, M, hist, fill,
+                                            out=(t.empty_like(frames), t.empty(self.n_streams, dtype=t.int32, device=dec.device), hist_out, fill_out))
+        status = None
+        if self._rs is not None:
+            _, status = dec.rs_decode(self._rs[0], out, n_out, 1)
+        if derandomize:
+            out, _, errors = dec.dvb_derandomize(out, n_out, phase, status, phase_out=phase_out)
+        return out, n_out, errors, status
 
     def _frame_out(self, n_bits):
         t, dec = self.decoder.torch, self.decoder
@@ -188,10 +245,18 @@ class MultiStreamDecoder:
 
     def take_frames(self) -> list:
         """per stream (frames uint8 [n][ceil(Q/8)], marker_errors int64 [n]) -- with rs= also rs_status int32 [n][I] --: the frames
-        completed since the last take, in order"""
+        completed since the last take, in order.
+        With deinterleave=(B, M) the first element holds the de-interleaved packets, uint8 [k][P/8]: packet k of a take is packet k of
+        the rule of vit_hip_deinterleave_batch over the packets extracted since the last (re-)lock, Reed-Solomon corrected with rs=.  The
+        second element is then still the marker_errors of the frames EXTRACTED since the last take, one per input packet, int64 [m] with m
+        >= k (the packets that fill the delay lines are counted too).  With dvb_derandomize=True the first element is the transport
+        packets, uint8 [k][188], by the rule of vit_hip_dvb_derandomize_batch, and the second their sync_errors, int64 [k]: the bits the
+        sync byte differed in from 0x47, or from 0xB8 at the head of a group of eight.  rs_status, int32 [k][1], is there exactly with
+        rs=."""
         if self._frames is None:
             raise AttributeError("this receiver was made without frames=True")
-        empty = (np.zeros((0, self._frames[1]), dtype=np.uint8), np.zeros(0, dtype=np.int64))
+        width = 188 if self._dvb is not None and self._dvb[2] else self._frames[1]
+        empty = (np.zeros((0, width), dtype=np.uint8), np.zeros(0, dtype=np.int64))
         if self._rs is not None:
             empty += (np.zeros((0, self._rs[1]), dtype=np.int32),)
         taken = []
@@ -269,16 +334,17 @@ class StreamDecoder(MultiStreamDecoder):
     """MultiStreamDecoder for ONE long stream: push() and finish() take any tensor of whole trellis steps ([steps][R], flat, or a view
     that is not contiguous) and return `bytes`; `.channel_errors` (with channel_errors=True) is a pair of ints, `.marker_totals` (with
     marker and period) a pair of [P] arrays and `.marker_lock` one (phase, inverted, errors, compared); take_frames() (with
-    frames=True) returns the one (frames, marker_errors) pair, or with rs= the one (frames, marker_errors, rs_status) triple."""
+    frames=True) returns the one (frames, marker_errors) pair, or with rs= the one (frames, marker_errors, rs_status) triple; with
+    deinterleave= / dvb_derandomize= what MultiStreamDecoder.take_frames says, for the one stream."""
 
     _RULE = "window, head, tail outside the argument rule of vit_hip_decode_stream"
     _SHAPE, _FINISHED, _EMPTY = "[steps][R]", "the stream is finished", "an empty stream"
 
     def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False,
                  marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0, frame_pad=None, rs=None,
-                 rs_interleave: int = 1):
+                 rs_interleave: int = 1, deinterleave=None, dvb_derandomize: bool = False):
         super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period, frames, frame_drop_bits, frame_pad, rs,
-                         rs_interleave)
+                         rs_interleave, deinterleave, dvb_derandomize)
 
     def take_frames(self):
         return super().take_frames()[0]
