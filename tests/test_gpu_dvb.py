@@ -494,4 +494,4 @@ def test_the_keywords_are_checked_and_change_nothing_when_absent():
     with pytest.raises(ValueError):
         StreamDecoder(dec, 1024, marker=DVB_SYNC, period=96, frames=True, deinterleave=(3, 2), dvb_derandomize=True)
     plain = StreamDecoder(dec, 1024, **kw)
-    assert plain._dvb is None and [x.shape for x in plain.take_frames()] == [(0, 204), (0,)]
+    assert plain._chain.branches is None and [x.shape for x in plain.take_frames()] == [(0, 204), (0,)]

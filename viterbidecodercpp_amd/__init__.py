@@ -1,7 +1,8 @@
 """viterbidecodercpp_amd -- MI355X (gfx950) implementation of the Viterbi update()+chainback() hot path.
 
 Product code: csrc/ (HIP kernels + C ABI, built to libvit_hip.so) and the host-side mirror of the reference's decoder
-interface in decoder.py, with the chunked stream receivers in stream.py.  codes.py / synth.py hold constants and synthetic-input generation for the measurement.
+interface in decoder.py -- the outer chain behind the decoder (marker search, frame extraction, Reed-Solomon, de-interleaver,
+derandomiser) in outer.py, the tensor rules of both in _args.py --, with the chunked stream receivers in stream.py.  codes.py / synth.py hold constants and synthetic-input generation for the measurement.
 """
 from .codes import COMMON_CODES, Code, DecoderConfig, get_decoding_config, SOFT16, SOFT8, HARD8  # noqa: F401
 from .decoder import (BatchDecoder, DecodePipeline, ViterbiBranchTable, ViterbiDecoder_Config, ViterbiDecoder_Core,  # noqa: F401

@@ -1,0 +1,90 @@
+"""The tensor rules of the Python host layer, each stated once: what decoder.py, outer.py and stream.py ask of a tensor before its address
+goes to the C ABI.  Plain functions; each raises ValueError and names the argument (`what`).  Where the call sites once differed, the rule
+is the more permissive of them, and says so."""
+import numpy as np
+
+
+def device(x, dtype, what):
+    """a CUDA tensor of `dtype`: the part every rule shares; its layout is the caller's to check"""
+    if x.dtype != dtype or not x.is_cuda:
+        raise ValueError(f"{what} must be a {dtype} CUDA tensor")
+    return x
+
+
+def dense(x, dtype, numel, what):
+    """a contiguous CUDA tensor of `dtype` with exactly `numel` elements (None: any number)"""
+    if not device(x, dtype, what).is_contiguous() or (numel is not None and x.numel() != numel):
+        raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor" + ("" if numel is None else f" of {numel} elements"))
+    return x
+
+
+def counts(x, rows, what):
+    """None, or one int32 per row"""
+    import torch
+    return x if x is None else dense(x, torch.int32, rows, what)
+
+
+def bit_rows(x, n_bits):
+    """(rows, row stride) of `bytes`: uint8, one row or [rows][>= ceil(n_bits/8)] with contiguous rows.  An empty tensor may have any
+    strides, and the stride of a single row is never used (0)"""
+    import torch
+    if device(x, torch.uint8, "bytes").dim() not in (1, 2) or (x.numel() and x.stride(-1) != 1):
+        raise ValueError("bytes must be one row or [rows][>= ceil(n_bits/8)] with contiguous rows")
+    if x.shape[-1] < (n_bits + 7) // 8:
+        raise ValueError(f"{n_bits} bits need {(n_bits + 7) // 8} bytes per row of bytes")
+    rows = 1 if x.dim() == 1 else int(x.shape[0])
+    return rows, (int(x.stride(0)) if rows > 1 else 0)
+
+
+def packets(x, what, least):
+    """(rows, max_frames, packet stride) of a uint8 tensor [rows][max_frames][>= least] or [max_frames][...] (one row) with evenly spaced
+    packets.  An empty tensor may have any strides; rows are only held to the spacing where there is more than one"""
+    import torch
+    if device(x, torch.uint8, what).dim() not in (2, 3) or (x.numel() and x.stride(-1) != 1) or x.shape[-1] < least:
+        raise ValueError(f"{what} must be [rows][max_frames][>= {least}] or [max_frames][...] with contiguous packets")
+    rows, mf = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2])
+    if x.dim() == 3 and rows > 1 and mf > 0 and x.stride(0) != mf * x.stride(1):
+        raise ValueError(f"{what} must be evenly spaced")
+    return rows, mf, (int(x.stride(-2)) if mf > 1 or rows > 1 else int(x.shape[-1]))
+
+
+def row_buffer(x, rows, least, what):
+    """the row stride of a uint8 buffer [rows][>= least] with contiguous rows that is carried from call to call; a single row's stride is
+    its width"""
+    import torch
+    if device(x, torch.uint8, what).dim() != 2 or x.shape[0] != rows or x.shape[1] < least or x.stride(1) != 1:
+        raise ValueError(f"{what} must be [{rows}][>= {least}] with contiguous rows")
+    return int(x.stride(0)) if rows > 1 else int(x.shape[1])
+
+
+def carried(prev, prev_count, nxt, rows, least, what, counted):
+    """the row stride of the row buffer `nxt` (`what`_out) a call writes and of `prev` (`what`), the one the call before wrote (None:
+    nothing carried): `prev` comes with its int32 counts [rows] (`counted`), is another tensor than `nxt` and has its row stride"""
+    stride = row_buffer(nxt, rows, least, f"{what}_out")
+    if prev is not None:
+        if counts(prev_count, rows, counted) is None:
+            raise ValueError(f"{what} needs {counted}, an int32 tensor [{rows}]")
+        if row_buffer(prev, rows, least, what) != stride or prev.data_ptr() == nxt.data_ptr():
+            raise ValueError(f"{what} and {what}_out must be distinct tensors with the same row stride")
+    return stride
+
+
+def state_tensor(torch, device, states, frames=None, what="start_state"):
+    """None, or the encoder / decoder states as a contiguous int32 tensor on `device`; with `frames`, flat and one per frame"""
+    if states is None:
+        return None
+    states = torch.as_tensor(states, dtype=torch.int32, device=device)
+    if frames is not None and states.numel() != frames:
+        raise ValueError(f"{what} must hold one state per frame")
+    return (states if frames is None else states.reshape(-1)).contiguous()
+
+
+def puncture_map(owner, mask):
+    """the int32 device tensor that names, per mother-code symbol of the boolean puncturing vector `mask`, the transmitted symbol it is
+    (-1: punctured).  Built and uploaded once per puncturing scheme: `owner` (its .torch, .device) keeps the last one"""
+    key = mask.tobytes()
+    cached = getattr(owner, "_puncture_map", None)
+    if cached is None or cached[0] != key:
+        idx = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
+        cached = owner._puncture_map = (key, owner.torch.from_numpy(idx).to(owner.device))
+    return cached[1]

@@ -19,8 +19,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
 from .codes import DecoderConfig
+from .outer import _OuterChain, _ptr
 
 
 def _parity(x: np.ndarray) -> np.ndarray:
@@ -293,32 +294,10 @@ class ViterbiDecoder_HIP:
         return rs + base.take_unreported_renormalisation()
 
 
-class _RsCode:
-    """a vit_hip_rs_code: the tables of one reed_solomon.RSCode on the device of a handle, which it keeps alive"""
-
-    def __init__(self, handle, code):
-        self._handle = handle
-        self._c = C.c_void_p()
-        params = _lib.VitHipRsParams(code.gfpoly, code.fcr, code.prim, code.nroots, code.pad, int(code.dual_basis))
-        _lib.check(_lib.load().vit_hip_rs_create(handle._h, C.byref(params), C.byref(self._c)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_c", None):
-                _lib.load().vit_hip_rs_destroy(self._c)
-                self._c = None
-        except Exception:
-            pass
-
-
-def _ptr(x):
-    """the address a tensor starts at, as the C ABI takes it; NULL for None"""
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
-class BatchDecoder:
+class BatchDecoder(_OuterChain):
     """Frame-parallel decoder on device-resident torch tensors (vit_hip_*_batch).  torch is plumbing only: it owns the
-    HBM buffers and the stream."""
+    HBM buffers and the stream.  The outer chain behind the decoder (marker_search, frames_extract, rs_decode, deinterleave,
+    dvb_derandomize) is mixed in from outer.py; the tensor rules of every method are those of _args.py."""
 
     def __init__(self, branch_table: ViterbiBranchTable = None, config: ViterbiDecoder_Config = None, device=0,
                  blob: bytes = None, plan: int = _lib.PLAN_AUTO):
@@ -383,13 +362,8 @@ class BatchDecoder:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _is_symbols(self, symbols):
-        return symbols.dtype == self._soft_dtype and symbols.is_cuda and symbols.is_contiguous()
-
     def _check_symbols(self, symbols, n_steps):
-        if not self._is_symbols(symbols):
-            raise ValueError(f"symbols must be a contiguous {self._soft_dtype} CUDA tensor")
-        frames = symbols.shape[0]
+        frames = _args.dense(symbols, self._soft_dtype, None, "symbols").shape[0]
         if symbols.numel() != frames * n_steps * self.R:
             raise ValueError("symbols must have shape [frames][n_steps][R]")
         return frames
@@ -406,9 +380,7 @@ class BatchDecoder:
         if want_metrics:
             met = t.empty((frames, self.N), dtype=self._error_dtype, device=self.device) if met is None else met
             rs = t.empty(frames, dtype=t.int64, device=self.device) if rs is None else rs
-        ss = None
-        if start_state is not None:
-            ss = t.as_tensor(start_state, dtype=t.int32, device=self.device).contiguous()
+        ss = _args.state_tensor(t, self.device, start_state)
         _lib.check(_lib.load().vit_hip_update_batch(
             self._handle._h, _ptr(symbols), frames, n_steps, L, _ptr(ws), ws.numel() * ws.element_size(), _ptr(met), _ptr(rs), _ptr(ss),
             self._stream()))
@@ -419,9 +391,7 @@ class BatchDecoder:
         starts from."""
         t = self.torch
         met = t.empty((frames, self.N), dtype=self._error_dtype, device=self.device) if metrics_out is None else metrics_out
-        ss = None
-        if start_state is not None:
-            ss = t.as_tensor(start_state, dtype=t.int32, device=self.device).contiguous()
+        ss = _args.state_tensor(t, self.device, start_state)
         _lib.check(_lib.load().vit_hip_reset_batch(self._handle._h, frames, _ptr(ss), _ptr(met), self._stream()))
         return met
 
@@ -436,9 +406,7 @@ class BatchDecoder:
         frames = metrics.shape[0]
         if n_steps is None:
             n_steps = symbols.shape[1]
-        if symbols.dtype != self._soft_dtype or not symbols.is_cuda:
-            raise ValueError(f"symbols must be a {self._soft_dtype} CUDA tensor")
-        if symbol_frame_stride == 0 and not symbols.is_contiguous():
+        if not _args.device(symbols, self._soft_dtype, "symbols").is_contiguous() and symbol_frame_stride == 0:
             raise ValueError("packed chunks must be contiguous (or pass symbol_frame_stride)")
         if metrics.dim() != 2 or metrics.shape[1] != self.N or not metrics.is_contiguous():
             raise ValueError("metrics must be a contiguous [frames][N] tensor")
@@ -463,9 +431,7 @@ class BatchDecoder:
         ws = self._workspace(frames, L, workspace)
         if out is None:
             out = t.empty((frames, (L + 7) // 8), dtype=t.uint8, device=self.device)
-        es = None
-        if end_state is not None:
-            es = t.as_tensor(end_state, dtype=t.int32, device=self.device).contiguous()
+        es = _args.state_tensor(t, self.device, end_state)
         if kernel is None:
             _lib.check(_lib.load().vit_hip_chainback_batch(self._handle._h, _ptr(ws), frames, L, _ptr(out), _ptr(es), self._stream()))
         else:
@@ -518,8 +484,8 @@ class BatchDecoder:
                 ok_out = t.empty(frames, dtype=t.uint8, device=self.device)
         for name, x, dt, n in (("out", out, t.uint8, frames * ((L + 7) // 8)), ("end_state_out", end_state_out, t.int32, frames),
                                ("ok_out", ok_out, t.uint8, frames)):
-            if x is not None and (x.dtype != dt or not x.is_cuda or not x.is_contiguous() or x.numel() != n):
-                raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor of {n} elements")
+            if x is not None:
+                _args.dense(x, dt, n, name)
         _lib.check(_lib.load().vit_hip_decode_tail_biting_batch(
             self._handle._h, _ptr(symbols), frames, L, head, tail, _ptr(ws), ws.numel() * ws.element_size(), _ptr(out), _ptr(end_state_out),
             _ptr(ok_out), self._stream()))
@@ -557,17 +523,14 @@ class BatchDecoder:
         steps run as one uniform batch."""
         t = self.torch
         window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
-        if not self._is_symbols(symbols) or symbols.numel() % self.R != 0:
-            raise ValueError(f"symbols must be a contiguous {self._soft_dtype} CUDA tensor of [steps][R]")
+        if _args.dense(symbols, self._soft_dtype, None, "symbols").numel() % self.R != 0:
+            raise ValueError("symbols must hold whole trellis steps, [steps][R]")
         T = symbols.numel() // self.R
         need = _lib.load().vit_hip_stream_workspace_bytes(self._handle._h, T, window, head, tail, flags)
         ws, nb = self._segment(need, workspace, T, head, tail, begin, end,
                                f"stream decoding needs head, tail >= K-1, window >= 8, head, tail, and a segment that emits bits "
                                f"(K = {self.K}, steps = {T}, window = {window}, head = {head}, tail = {tail})")
-        if out is None:
-            out = t.empty(nb, dtype=t.uint8, device=self.device)
-        elif out.dtype != t.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != nb:
-            raise ValueError(f"out must be a contiguous uint8 CUDA tensor of {nb} elements")
+        out = t.empty(nb, dtype=t.uint8, device=self.device) if out is None else _args.dense(out, t.uint8, nb, "out")
         n_bits = C.c_size_t(0)
         _lib.check(_lib.load().vit_hip_decode_stream(
             self._handle._h, _ptr(symbols), T, window, head, tail, flags, _ptr(ws), ws.numel() * ws.element_size(), _ptr(out),
@@ -589,8 +552,8 @@ class BatchDecoder:
         ceil(n_bits/8) are left as they are and the view of the written part is returned."""
         t = self.torch
         window, head, tail, flags = self._stream_args(window, head, tail, begin, end)
-        if not self._is_symbols(symbols) or symbols.dim() != 3 or symbols.shape[2] != self.R:
-            raise ValueError(f"symbols must be a contiguous {self._soft_dtype} CUDA tensor of [n_streams][pitch][R]")
+        if _args.dense(symbols, self._soft_dtype, None, "symbols").dim() != 3 or symbols.shape[2] != self.R:
+            raise ValueError("symbols must be [n_streams][pitch][R]")
         n_streams, pitch = int(symbols.shape[0]), int(symbols.shape[1])
         T = pitch if steps is None else int(steps)
         need = _lib.load().vit_hip_streams_workspace_bytes(self._handle._h, n_streams, pitch, T, window, head, tail, flags)
@@ -600,9 +563,9 @@ class BatchDecoder:
                                f"window = {window}, head = {head}, tail = {tail})")
         if out is None:
             out = t.empty((n_streams, nb), dtype=t.uint8, device=self.device)
-        elif (out.dtype != t.uint8 or not out.is_cuda or out.dim() != 2 or out.shape[0] != n_streams or out.shape[1] < nb
-              or out.stride(1) != 1 or (n_streams > 1 and out.stride(0) < nb)):
-            raise ValueError(f"out must be a uint8 CUDA tensor of [{n_streams}][>= {nb}] with contiguous rows")
+        elif (_args.device(out, t.uint8, "out").dim() != 2 or out.shape[0] != n_streams or out.shape[1] < nb or out.stride(1) != 1
+              or (n_streams > 1 and out.stride(0) < nb)):
+            raise ValueError(f"out must be [{n_streams}][>= {nb}] with contiguous rows")
         n_bits = C.c_size_t(0)
         _lib.check(_lib.load().vit_hip_decode_streams(
             self._handle._h, _ptr(symbols), n_streams, pitch, T, window, head, tail, flags, _ptr(ws), ws.numel() * ws.element_size(),
@@ -617,17 +580,9 @@ class BatchDecoder:
         mask = np.asarray(mask).astype(bool).reshape(-1)
         if mask.size % self.R != 0:
             raise ValueError("the puncturing vector must cover whole trellis steps (a multiple of R symbols)")
-        if not (punctured.is_cuda and punctured.dim() == 2 and punctured.is_contiguous()):
-            raise ValueError("punctured symbols must be a contiguous [frames][P] device tensor")
-        if punctured.dtype != self._soft_dtype or punctured.shape[1] != int(mask.sum()):
-            raise ValueError("punctured symbols: wrong dtype or count for this puncturing vector")
-        key = mask.tobytes()
-        cached = getattr(self, "_depuncture_map", None)
-        if cached is None or cached[0] != key:             # the map is per puncturing scheme: build and upload it once
-            idx = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
-            cached = (key, t.from_numpy(idx).to(self.device))
-            self._depuncture_map = cached
-        d_idx = cached[1]
+        if _args.dense(punctured, self._soft_dtype, None, "punctured").dim() != 2 or punctured.shape[1] != int(mask.sum()):
+            raise ValueError("punctured must be [frames][P] with the P symbols this puncturing vector keeps")
+        d_idx = _args.puncture_map(self, mask)
         frames = punctured.shape[0]
         if out is None:
             out = t.empty((frames, mask.size // self.R, self.R), dtype=self._soft_dtype, device=self.device)
@@ -666,8 +621,8 @@ class BatchDecoder:
         flags = _lib.ENCODE_TAIL_BITING if tail_biting else (_lib.ENCODE_TAIL if tail else 0)
         steps = L + (self.K - 1 if flags == _lib.ENCODE_TAIL else 0)
         nb = (L + 7) // 8
-        if bytes.dtype != t.uint8 or not bytes.is_cuda or bytes.dim() not in (1, 2) or bytes.stride(-1) != 1:
-            raise ValueError("bytes must be a uint8 CUDA tensor [frames][>= ceil(L/8)] (or one frame's bytes) with contiguous rows")
+        if _args.device(bytes, t.uint8, "bytes").dim() not in (1, 2) or bytes.stride(-1) != 1:
+            raise ValueError("bytes must be [frames][>= ceil(L/8)] (or one frame's bytes) with contiguous rows")
         if bytes.dim() == 2:
             frames = int(bytes.shape[0])
             stride = int(bytes_frame_stride) or (int(bytes.stride(0)) if frames > 1 else int(bytes.shape[1]))
@@ -678,12 +633,7 @@ class BatchDecoder:
             frames = (bytes.numel() - nb) // stride + 1 if bytes.numel() >= nb else 0
         if frames < 1 or stride < nb:
             raise ValueError(f"bytes holds no frame of {nb} bytes at stride {stride}")
-        ss = None
-        if start_state is not None:
-            ss = t.as_tensor(start_state, dtype=t.int32, device=self.device).reshape(-1).contiguous()
-            if ss.numel() != frames:
-                raise ValueError("start_state must hold one state per frame")
-        return frames, flags, steps, stride, ss
+        return frames, flags, steps, stride, _args.state_tensor(t, self.device, start_state, frames)
 
     def encode(self, bytes, L: int, tail=True, tail_biting=False, start_state=None, out=None, end_state_out=False):
         """the convolutional encoder on device-resident info bytes (vit_hip_encode_batch): bytes [F][>= ceil(L/8)] uint8, MSB-first
@@ -698,9 +648,7 @@ class BatchDecoder:
         n = steps * self.R
         if out is None:
             out = t.empty((frames, steps, self.R), dtype=self._soft_dtype, device=self.device)
-        if out.dtype != self._soft_dtype or not out.is_cuda:
-            raise ValueError(f"out must be a {self._soft_dtype} CUDA tensor")
-        if out.is_contiguous() and out.numel() == frames * n:
+        if _args.device(out, self._soft_dtype, "out").is_contiguous() and out.numel() == frames * n:
             sstride = n
         elif out.dim() == 2 and out.shape[0] == frames and out.shape[1] >= n and out.stride(1) == 1 and (frames == 1 or out.stride(0) >= n):
             sstride = int(out.stride(0)) if frames > 1 else n
@@ -709,8 +657,7 @@ class BatchDecoder:
         es = None
         if end_state_out is not False and end_state_out is not None:
             es = t.empty(frames, dtype=t.int32, device=self.device) if end_state_out is True else end_state_out
-            if es.dtype != t.int32 or not es.is_cuda or not es.is_contiguous() or es.numel() != frames:
-                raise ValueError(f"end_state_out must be a contiguous int32 CUDA tensor of {frames} elements")
+            _args.dense(es, t.int32, frames, "end_state_out")
         _lib.check(_lib.load().vit_hip_encode_batch(
             self._handle._h, _ptr(bytes), bstride, frames, L, flags, _ptr(ss), _ptr(out), sstride, _ptr(es), self._stream()))
         return (out, es) if es is not None else out
@@ -727,8 +674,8 @@ class BatchDecoder:
         t = self.torch
         frames, flags, steps, bstride, ss = self._encode_args(bytes, L, tail, tail_biting, start_state, bytes_frame_stride)
         n = steps * self.R
-        if symbols.dtype != self._soft_dtype or not symbols.is_cuda or symbols.stride(-1) != 1:
-            raise ValueError(f"symbols must be a {self._soft_dtype} CUDA tensor whose last dimension is contiguous")
+        if _args.device(symbols, self._soft_dtype, "symbols").stride(-1) != 1:
+            raise ValueError("the last dimension of symbols must be contiguous")
         sstride = int(symbol_frame_stride)
         if sstride == 0:
             if symbols.is_contiguous() and symbols.numel() == frames * n:
@@ -750,8 +697,8 @@ class BatchDecoder:
     def _sync_args(self, received, hypotheses, mask):
         """(hypothesis array, count, source map tensor or None, period_symbols, kept_per_period) of a sync_build / sync_search call"""
         t = self.torch
-        if received.dtype != self._soft_dtype or not received.is_cuda or received.dim() != 1 or not received.is_contiguous():
-            raise ValueError(f"received must be a contiguous 1-D {self._soft_dtype} CUDA tensor")
+        if _args.dense(received, self._soft_dtype, None, "received").dim() != 1:
+            raise ValueError("received must be 1-D")
         hyps = [(int(o), int(f)) for o, f in hypotheses]
         if not 1 <= len(hyps) <= _lib.SYNC_MAX_HYPOTHESES:
             raise ValueError(f"1 to {_lib.SYNC_MAX_HYPOTHESES} hypotheses per call")
@@ -761,13 +708,7 @@ class BatchDecoder:
         mask = np.asarray(mask).astype(bool).reshape(-1)
         if mask.size == 0 or mask.size % self.R != 0 or not mask.any():
             raise ValueError("the puncturing mask must cover whole trellis steps (a multiple of R symbols) and keep a symbol")
-        key = mask.tobytes()
-        cached = getattr(self, "_sync_map", None)
-        if cached is None or cached[0] != key:             # the map is per puncturing scheme: build and upload it once
-            idx = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
-            cached = (key, t.from_numpy(idx).to(self.device))
-            self._sync_map = cached
-        return arr, len(hyps), cached[1], mask.size, int(mask.sum())
+        return arr, len(hyps), _args.puncture_map(self, mask), mask.size, int(mask.sum())
 
     def sync_build(self, received, hypotheses, steps: int, mask=None, pitch: int = None, out=None):
         """the [steps][R] stream of every alignment hypothesis from ONE received buffer (vit_hip_sync_build): hypotheses is a
@@ -781,8 +722,8 @@ class BatchDecoder:
         pitch = steps if pitch is None else int(pitch)
         if out is None:
             out = t.empty((n, pitch, self.R), dtype=self._soft_dtype, device=self.device)
-        elif not self._is_symbols(out) or out.numel() != n * pitch * self.R:
-            raise ValueError(f"out must be a contiguous {self._soft_dtype} CUDA tensor of [{n}][{pitch}][{self.R}]")
+        else:
+            _args.dense(out, self._soft_dtype, n * pitch * self.R, "out")
         _lib.check(_lib.load().vit_hip_sync_build(self._handle._h, _ptr(received), received.numel(), _ptr(d_idx), period, kept, arr, n,
                                                   steps, pitch, _ptr(out), self._stream()))
         return out
@@ -814,243 +755,6 @@ class BatchDecoder:
             self._handle._h, _ptr(received), received.numel(), _ptr(d_idx), period, kept, arr, n, steps, window, head, tail, _ptr(ws),
             ws.numel() * ws.element_size(), _ptr(err), _ptr(cmp), _ptr(best), self._stream()))
         return err, cmp, best
-
-    def marker_search(self, bytes, n_bits: int, marker: int, marker_bits: int, period: int, phase0: int = 0, history=None,
-                      history_bits: int = 0, out=None, accumulate=False):
-        """frame synchronisation (vit_hip_marker_search): the Hamming distance of the sync marker (`marker_bits` bits, the first
-        transmitted in the highest; frame_sync.CCSDS_ASM, DVB_SYNC) to every bit position of the decoded `bytes` -- uint8 CUDA, one
-        row or [rows][>= ceil(n_bits/8)] with its row stride, MSB-first as the decode calls write them --, summed per phase of the
-        frame period: position p belongs to phase (phase0 + p) mod period.  history [rows] (ints or a tensor): the `history_bits`
-        <= 63 stream bits in front of bit 0, the latest in bit 0, so that positions straddling two calls are counted.  returns
-        (distance, count, lock): int32 CUDA tensors [rows][period], [rows][period] and [rows][4] = (phase, inverted, errors,
-        compared) of the candidate with the lowest errors / compared (compared = marker_bits * count; inverted: errors = compared -
-        distance; the lower phase, then upright, on a tie).  out = (distance, count, lock) reuses those tensors; with
-        accumulate=True the call adds to the totals they hold and the lock is that of the totals.  Nothing is copied to the host."""
-        t = self.torch
-        if bytes.dtype != t.uint8 or not bytes.is_cuda or bytes.dim() not in (1, 2) or (bytes.numel() and bytes.stride(-1) != 1):
-            raise ValueError("bytes must be a uint8 CUDA tensor, one row or [rows][>= ceil(n_bits/8)] with contiguous rows")
-        n_bits, period, nb = int(n_bits), int(period), (int(n_bits) + 7) // 8
-        rows = 1 if bytes.dim() == 1 else int(bytes.shape[0])
-        if bytes.shape[-1] < nb:
-            raise ValueError(f"{n_bits} bits need {nb} bytes per row")
-        stride = int(bytes.stride(0)) if bytes.dim() == 2 and rows > 1 else 0
-        if period < 1 or period >= 1 << 31:
-            raise ValueError("period must be 1 .. 2^31 - 1")
-        hist = None
-        if history_bits:
-            if history is None:
-                raise ValueError("history_bits > 0 needs the history words")
-            if t.is_tensor(history):
-                hist = history.to(device=self.device, dtype=t.int64).reshape(-1).contiguous()
-            else:
-                words = np.asarray([int(x) for x in np.asarray(history, dtype=object).reshape(-1)], dtype=np.uint64)
-                hist = t.from_numpy(words.view(np.int64)).to(self.device)
-            if hist.numel() != rows:
-                raise ValueError("history must hold one word per row")
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True adds to the totals of out=(distance, count, lock)")
-            out = (t.empty((rows, period), dtype=t.int32, device=self.device), t.empty((rows, period), dtype=t.int32, device=self.device),
-                   t.empty((rows, 4), dtype=t.int32, device=self.device))
-        distance, count, lock = out
-        for x, n in ((distance, rows * period), (count, rows * period), (lock, rows * 4)):
-            if x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != n:
-                raise ValueError(f"out must be contiguous int32 CUDA tensors of [{rows}][{period}], [{rows}][{period}] and [{rows}][4]")
-        _lib.check(_lib.load().vit_hip_marker_search(
-            self._handle._h, _ptr(bytes), stride, rows, n_bits, int(marker), int(marker_bits), _ptr(hist), int(history_bits), period,
-            int(phase0), _lib.MARKER_ACCUMULATE if accumulate else 0, _ptr(distance), _ptr(count), _ptr(lock), self._stream()))
-        return distance, count, lock
-
-    def frames_capacity(self, n_bits: int, period: int) -> int:
-        """the most frames one frames_extract call over n_bits bits per row can complete: ceil(n_bits / period)"""
-        return int(_lib.load().vit_hip_frames_capacity(int(n_bits), int(period)))
-
-    def frames_extract(self, bytes, n_bits: int, period: int, phase0: int, lock, carry=None, carry_bits=None, marker: int = 0,
-                       marker_bits: int = 0, drop_bits: int = 0, pad=None, max_frames: int = None, out=None):
-        """frame extraction (vit_hip_frames_extract): the frames of the decoded `bytes` -- uint8 CUDA, one row or [rows][>=
-        ceil(n_bits/8)], MSB-first, bit 0 at phase `phase0` of the frame period -- cut at `lock`, the int32 [rows][4] tensor
-        marker_search returns (read on the device: phase and inverted).  carry / carry_bits: the uint8 [rows][>= ceil((period-1)/8)]
-        and int32 [rows] the previous call returned as carry_out / carry_bits_out (None: nothing carried).  A frame is complemented
-        under an inverted lock, loses its first `drop_bits` bits (the marker) and is XORed with `pad`, uint8 CUDA [ceil(Q/8)] for its Q
-        = period - drop_bits output bits (frame_sync.ccsds_randomizer; None: none).  returns (frames, n_frames, marker_errors,
-        carry_out, carry_bits_out): uint8 [rows][max_frames][ceil(Q/8)] of which the first n_frames[r] (int32 [rows]) of row r are
-        written, int32 [rows][max_frames] = the bits of `marker` (marker_bits <= 64; 0: off, and None is returned) each written frame
-        differs in, and the unfinished frame's raw bits with their number.  max_frames defaults to frames_capacity(n_bits, period).
-        out = the same five reuses those tensors (frames may have a larger last dimension: its stride is the frame stride); carry
-        and carry_out must be distinct and have the same row stride.  Nothing is copied to the host."""
-        t = self.torch
-        if bytes.dtype != t.uint8 or not bytes.is_cuda or bytes.dim() not in (1, 2) or (bytes.numel() and bytes.stride(-1) != 1):
-            raise ValueError("bytes must be a uint8 CUDA tensor, one row or [rows][>= ceil(n_bits/8)] with contiguous rows")
-        n_bits, period, drop_bits, marker_bits = int(n_bits), int(period), int(drop_bits), int(marker_bits)
-        rows = 1 if bytes.dim() == 1 else int(bytes.shape[0])
-        if bytes.shape[-1] < (n_bits + 7) // 8:
-            raise ValueError(f"{n_bits} bits need {(n_bits + 7) // 8} bytes per row")
-        if not 8 <= period < 1 << 31 or not 0 <= drop_bits < period or n_bits < 1:
-            raise ValueError("period must be 8 .. 2^31 - 1, drop_bits below it, n_bits at least 1")
-        stride = int(bytes.stride(0)) if bytes.dim() == 2 and rows > 1 else 0
-        qb, cb = (period - drop_bits + 7) // 8, (period - 1 + 7) // 8
-        cap = self.frames_capacity(n_bits, period)
-        max_frames = cap if max_frames is None else int(max_frames)
-        if lock.dtype != t.int32 or not lock.is_cuda or not lock.is_contiguous() or lock.numel() != rows * 4:
-            raise ValueError(f"lock must be the contiguous int32 CUDA tensor [{rows}][4] marker_search returns")
-        if out is None:
-            out = (t.empty((rows, max_frames, qb), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device),
-                   t.empty((rows, max_frames), dtype=t.int32, device=self.device) if marker_bits else None,
-                   t.empty((rows, cb), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device))
-        frames, n_frames, marker_errors, carry_out, carry_bits_out = out
-        if (frames.dtype != t.uint8 or not frames.is_cuda or frames.dim() != 3 or tuple(frames.shape[:2]) != (rows, max_frames)
-                or frames.shape[2] < qb or frames.stride(2) != 1 or (rows > 1 and frames.stride(0) != max_frames * frames.stride(1))):
-            raise ValueError(f"out[0] must be a uint8 CUDA tensor [{rows}][{max_frames}][>= {qb}] with evenly spaced frames")
-        for x, n in ((n_frames, rows), (marker_errors, rows * max_frames), (carry_bits_out, rows)):
-            if x is not None and (x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != n):
-                raise ValueError(f"out must hold contiguous int32 CUDA tensors of [{rows}], [{rows}][{max_frames}] and [{rows}]")
-        for x in (carry_out, carry):
-            if x is not None and (x.dtype != t.uint8 or not x.is_cuda or x.dim() != 2 or x.shape[0] != rows or x.shape[1] < cb
-                                  or x.stride(1) != 1):
-                raise ValueError(f"a carry must be a uint8 CUDA tensor [{rows}][>= {cb}] with contiguous rows")
-        cstride = int(carry_out.stride(0)) if rows > 1 else int(carry_out.shape[1])
-        if carry is not None:
-            if (carry_bits is None or carry_bits.dtype != t.int32 or not carry_bits.is_cuda or not carry_bits.is_contiguous()
-                    or carry_bits.numel() != rows):
-                raise ValueError(f"carry needs carry_bits, a contiguous int32 CUDA tensor [{rows}]")
-            if (int(carry.stride(0)) if rows > 1 else int(carry.shape[1])) != cstride or carry.data_ptr() == carry_out.data_ptr():
-                raise ValueError("carry and carry_out must be distinct tensors with the same row stride")
-        if pad is not None and (pad.dtype != t.uint8 or not pad.is_cuda or not pad.is_contiguous() or pad.numel() < qb):
-            raise ValueError(f"pad must be a contiguous uint8 CUDA tensor of at least {qb} bytes")
-        _lib.check(_lib.load().vit_hip_frames_extract(
-            self._handle._h, _ptr(bytes), stride, rows, n_bits, period, int(phase0), _ptr(lock), _ptr(carry),
-            _ptr(carry_bits) if carry is not None else None, cstride, int(marker), marker_bits, drop_bits, _ptr(pad), _ptr(frames),
-            int(frames.stride(1)), max_frames, _ptr(n_frames), _ptr(marker_errors), _ptr(carry_out), _ptr(carry_bits_out), self._stream()))
-        return frames, n_frames, marker_errors, carry_out, carry_bits_out
-
-    def _rs_code(self, code):
-        """the vit_hip_rs_code of an RSCode: made at its first use, kept as long as this decoder"""
-        if code not in self._rs_codes:
-            self._rs_codes[code] = _RsCode(self._handle, code)
-        return self._rs_codes[code]
-
-    def rs_decode(self, code, frames, n_frames=None, interleave: int = 1, out=None, status=None):
-        """Reed-Solomon decoding (vit_hip_rs_decode_batch) of `frames`, the uint8 CUDA tensor [rows][max_frames][>= n * interleave]
-        frames_extract returns (or [max_frames][...]: one row; the last stride is the frame stride): `code` is a reed_solomon.RSCode,
-        symbol i of codeword c is frame byte i * interleave + c.  n_frames: the int32 CUDA tensor [rows] frames_extract returns -- frames
-        at or behind it are neither read nor written, and neither is their status -- or None: all of them.  out: None decodes in place,
-        or a tensor of the same shape and strides that does not overlap `frames`.  returns (frames, status): the tensor written and
-        int32 [rows][max_frames][interleave], the byte errors corrected in each codeword or -1 where more than t = nroots // 2 stand in
-        it (that codeword is left as received).  status = an int32 tensor of that size reuses it.  Nothing is copied to the host."""
-        t = self.torch
-        I = int(interleave)
-        if frames.dtype != t.uint8 or not frames.is_cuda or frames.dim() not in (2, 3) or (frames.numel() and frames.stride(-1) != 1):
-            raise ValueError("frames must be a uint8 CUDA tensor [rows][max_frames][>= n * interleave] or [max_frames][...]")
-        rows = 1 if frames.dim() == 2 else int(frames.shape[0])
-        max_frames = int(frames.shape[-2])
-        if I < 1 or frames.shape[-1] < code.n * I:
-            raise ValueError(f"a frame of {code.n} * {I} bytes does not fit the last dimension")
-        if frames.dim() == 3 and rows > 1 and max_frames > 0 and frames.stride(0) != max_frames * frames.stride(1):
-            raise ValueError("frames must be evenly spaced")
-        stride = int(frames.stride(-2)) if max_frames > 1 or rows > 1 else int(frames.shape[-1])
-        out = frames if out is None else out
-        if out is not frames and (out.dtype != t.uint8 or not out.is_cuda or out.shape != frames.shape or out.stride() != frames.stride()):
-            raise ValueError("out must be a uint8 CUDA tensor with the shape and strides of frames")
-        if n_frames is not None and (n_frames.dtype != t.int32 or not n_frames.is_cuda or not n_frames.is_contiguous() or n_frames.numel() != rows):
-            raise ValueError(f"n_frames must be a contiguous int32 CUDA tensor [{rows}]")
-        if status is None:
-            status = t.empty(tuple(frames.shape[:-1]) + (I,), dtype=t.int32, device=self.device)
-        elif status.dtype != t.int32 or not status.is_cuda or not status.is_contiguous() or status.numel() != rows * max_frames * I:
-            raise ValueError(f"status must be a contiguous int32 CUDA tensor of {rows} * {max_frames} * {I} entries")
-        _lib.check(_lib.load().vit_hip_rs_decode_batch(self._handle._h, self._rs_code(code)._c, _ptr(frames), _ptr(out), stride, rows, max_frames,
-                                                       _ptr(n_frames), I, _ptr(status), self._stream()))
-        return out, status
-
-    def _packets(self, x, what, least):
-        """(rows, max_frames, packet stride) of a uint8 CUDA tensor [rows][max_frames][>= least] or [max_frames][...] with evenly spaced packets"""
-        t = self.torch
-        if x.dtype != t.uint8 or not x.is_cuda or x.dim() not in (2, 3) or (x.numel() and x.stride(-1) != 1) or x.shape[-1] < least:
-            raise ValueError(f"{what} must be a uint8 CUDA tensor [rows][max_frames][>= {least}] or [max_frames][...]")
-        rows, mf = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2])
-        if x.dim() == 3 and rows > 1 and mf > 0 and x.stride(0) != mf * x.stride(1):
-            raise ValueError(f"{what} must be evenly spaced")
-        return rows, mf, (int(x.stride(-2)) if mf > 1 or rows > 1 else int(x.shape[-1]))
-
-    def _counts(self, x, rows, what):
-        t = self.torch
-        if x is not None and (x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != rows):
-            raise ValueError(f"{what} must be a contiguous int32 CUDA tensor [{rows}]")
-        return x
-
-    def deinterleave(self, packets, n_frames=None, branches: int = 12, cell: int = 17, hist=None, fill=None, packet_bytes: int = None,
-                     out=None):
-        """the convolutional (Forney) de-interleaver (vit_hip_deinterleave_batch; dvb.DVB_INTERLEAVER = (12, 17)) on `packets`, the
-        uint8 CUDA tensor [rows][max_frames][>= n] frames_extract returns (or [max_frames][...]: one row; n = packet_bytes, by default
-        the last dimension, a multiple of branches).  n_frames: the int32 CUDA tensor [rows] frames_extract returns, or None: all.
-        hist / fill: the uint8 [rows][H n] and int32 [rows] the previous call returned as hist_out / fill_out (None: nothing carried), H
-        = ceil((branches-1) cell branches / n).  returns (out, n_out, hist_out, fill_out): uint8 of the shape of `packets` of which the
-        first n_out[r] (int32 [rows]) packets of row r are written -- byte i of packet k is stream byte (H + k) n + i - (branches-1 - i
-        mod branches) cell branches of the real history packets followed by the input --, as rs_decode(interleave=1) takes them, and the
-        last min(H, all) packets of that stream with their number.  out = the same four reuses those tensors; hist and hist_out must be
-        distinct and have the same row stride.  Nothing is copied to the host."""
-        t = self.torch
-        B, M = int(branches), int(cell)
-        n = int(packets.shape[-1]) if packet_bytes is None else int(packet_bytes)
-        rows, mf, stride = self._packets(packets, "packets", n)
-        if B < 2 or M < 1 or n < 1 or n % B:
-            raise ValueError("branches must be at least 2, cell at least 1, packet_bytes a multiple of branches")
-        H = -(-(B - 1) * M * B // n)
-        if out is None:
-            out = (t.empty(tuple(packets.shape[:-1]) + (n,), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device),
-                   t.empty((rows, H * n), dtype=t.uint8, device=self.device), t.empty(rows, dtype=t.int32, device=self.device))
-        d_out, n_out, hist_out, fill_out = out
-        orows, omf, ostride = self._packets(d_out, "out[0]", n)
-        if (orows, omf) != (rows, mf):
-            raise ValueError(f"out[0] must hold [{rows}][{mf}] packets")
-        self._counts(n_frames, rows, "n_frames"), self._counts(n_out, rows, "out[1]"), self._counts(fill_out, rows, "out[3]")
-        for x in (hist_out, hist):
-            if x is not None and (x.dtype != t.uint8 or not x.is_cuda or x.dim() != 2 or x.shape[0] != rows or x.shape[1] < H * n or x.stride(1) != 1):
-                raise ValueError(f"a history must be a uint8 CUDA tensor [{rows}][>= {H * n}] with contiguous rows")
-        hstride = int(hist_out.stride(0)) if rows > 1 else int(hist_out.shape[1])
-        if hist is not None:
-            if self._counts(fill, rows, "fill") is None:
-                raise ValueError("hist needs fill")
-            if (int(hist.stride(0)) if rows > 1 else int(hist.shape[1])) != hstride or hist.data_ptr() == hist_out.data_ptr():
-                raise ValueError("hist and hist_out must be distinct tensors with the same row stride")
-        _lib.check(_lib.load().vit_hip_deinterleave_batch(
-            self._handle._h, _ptr(packets), stride, rows, mf, _ptr(n_frames), B, M, n, _ptr(hist), _ptr(fill) if hist is not None else None,
-            hstride, _ptr(d_out), ostride, _ptr(n_out), _ptr(hist_out), _ptr(fill_out), self._stream()))
-        return d_out, n_out, hist_out, fill_out
-
-    def dvb_derandomize(self, packets, n_frames=None, phase=None, rs_status=None, out=None, phase_out=None, sync_errors=None,
-                        in_place: bool = False):
-        """DVB-S energy-dispersal removal (vit_hip_dvb_derandomize_batch) on `packets`, uint8 CUDA [rows][max_frames][>= 188] (or
-        [max_frames][...]: one row), of which the first 188 bytes of each are read -- 204-byte packets as rs_decode left them are fine.
-        n_frames: int32 CUDA [rows] or None: all.  phase: int32 CUDA [rows], the place 0 .. 7 of packet 0 in its group of eight; a
-        value outside (-1, say) or None means unknown: voted from this call's sync bytes.  rs_status: the int32 [rows][max_frames][1]
-        rs_decode returned, or None: where negative, the packet's transport_error_indicator is set.  returns (out, phase_out,
-        sync_errors): uint8 [rows][max_frames][188] of which the packets below n_frames are written -- byte 0 de-inverted at the head of
-        a group, bytes 1 .. 187 XORed with dvb.dvb_prbs() --, int32 [rows] = the phase of the next call's packet 0 (-1 while unknown: a
-        row without packets), int32 [rows][max_frames] = the bits the sync byte differs in from 0x47 (0xB8 at the head of a group).
-        out / phase_out / sync_errors reuse tensors; in_place=True writes into `packets` (one workgroup per row: slower on long rows).
-        Nothing is copied to the host."""
-        t = self.torch
-        rows, mf, stride = self._packets(packets, "packets", 188)
-        if in_place:
-            if out is not None:
-                raise ValueError("in_place=True writes into packets: no out")
-            d_out, ostride = packets, stride
-        else:
-            d_out = t.empty(tuple(packets.shape[:-1]) + (188,), dtype=t.uint8, device=self.device) if out is None else out
-            orows, omf, ostride = self._packets(d_out, "out", 188)
-            if (orows, omf) != (rows, mf):
-                raise ValueError(f"out must hold [{rows}][{mf}] packets")
-        self._counts(n_frames, rows, "n_frames"), self._counts(phase, rows, "phase")
-        phase_out = t.empty(rows, dtype=t.int32, device=self.device) if phase_out is None else self._counts(phase_out, rows, "phase_out")
-        if sync_errors is None:
-            sync_errors = t.empty(tuple(packets.shape[:-1]), dtype=t.int32, device=self.device)
-        for x, what in ((sync_errors, "sync_errors"), (rs_status, "rs_status")):
-            if x is not None and (x.dtype != t.int32 or not x.is_cuda or not x.is_contiguous() or x.numel() != rows * mf):
-                raise ValueError(f"{what} must be a contiguous int32 CUDA tensor of {rows} * {mf} entries")
-        _lib.check(_lib.load().vit_hip_dvb_derandomize_batch(
-            self._handle._h, _ptr(packets), stride, int(packets.shape[-1]), rows, mf, _ptr(n_frames), _ptr(phase), _ptr(rs_status), _ptr(d_out),
-            ostride, _ptr(phase_out), _ptr(sync_errors), self._stream()))
-        return d_out, phase_out, sync_errors
 
     def export_decisions(self, frames: int, L: int, n_steps: int = None, workspace=None, first_frame: int = 0):
         """decision history in the reference layout: int64 tensor [F][n_steps][W] (bit pattern of uint64 words).  The

@@ -1,13 +1,15 @@
 """The chunked receivers on top of BatchDecoder.decode_streams: push() symbols as they arrive, get decoded bytes back.
 
-`MultiStreamDecoder` serves n lockstep streams and holds everything there is to a receiver: the hold-back rule, the log of internal
-calls, the sub-byte carry, the running channel error totals and the first / done state.  `StreamDecoder` is its n_streams = 1 face
+`MultiStreamDecoder` serves n lockstep streams and holds what there is to chunking: the hold-back rule, the log of internal calls, the
+sub-byte carry, the running channel error and marker totals and the first / done state.  What happens to the emitted bits behind the
+marker search -- frames, de-interleaver, Reed-Solomon, derandomiser -- is one `_FrameChain`.  `StreamDecoder` is the n_streams = 1 face
 (vit_hip_decode_streams with one stream launches exactly what vit_hip_decode_stream launches).
 """
 from __future__ import annotations
 
 import numpy as np
 
+from . import _args
 from .decoder import BatchDecoder
 
 
@@ -17,6 +19,106 @@ def _next_states(states, bits, K):
     for j in range(max(bits.shape[1] - (K - 1), 0), bits.shape[1]):
         states = (states << 1) | bits[:, j].astype(np.int64)
     return states & ((1 << (K - 1)) - 1)
+
+
+class _FrameChain:
+    """What a receiver does on the device with the bits of an internal call behind the marker search: extract -> [de-interleave] ->
+    [Reed-Solomon] -> [derandomise], with the state each stage carries from call to call in two buffers it reads and writes in turn, and
+    the frames that came out, per stream, until take() hands them over.  `branches` and `cell` are None without de-interleaver, `rs` is
+    None without Reed-Solomon code; `packet_bytes` = period / 8 is the de-interleaver's packet."""
+
+    def __init__(self, decoder, n_streams, frames, marker, marker_bits, period, drop_bits, pad, rs, rs_interleave, deinterleave, derandomize):
+        if not frames or marker is None or not 8 <= int(period) or not 0 <= int(drop_bits) < int(period) or marker_bits > int(period):
+            raise ValueError("frames=True (rs=, deinterleave= and dvb_derandomize= need it) needs marker=(value, bits), period=P >= max(8, bits) "
+                             "and 0 <= frame_drop_bits < P")
+        t, n, P = decoder.torch, n_streams, int(period)
+        self.decoder, self.n_streams, self.marker, self.marker_bits, self.period, self.drop_bits = decoder, n, marker, marker_bits, P, int(drop_bits)
+        self.frame_bytes = (P - self.drop_bits + 7) // 8
+        self.pad = None
+        if pad is not None:
+            pad = pad if t.is_tensor(pad) else t.from_numpy(np.frombuffer(bytes(pad), dtype=np.uint8).copy())
+            self.pad = pad.to(device=decoder.device, dtype=t.uint8).reshape(-1).contiguous()
+            if self.pad.numel() < self.frame_bytes:
+                raise ValueError(f"frame_pad must hold ceil((period - frame_drop_bits) / 8) = {self.frame_bytes} bytes")
+        self.rs, self.rs_interleave = rs, int(rs_interleave)
+        if rs is not None and (self.rs_interleave < 1 or P - self.drop_bits != 8 * rs.n * self.rs_interleave):
+            raise ValueError("rs= needs frames=True and (period - frame_drop_bits) / 8 == rs.n * rs_interleave")
+        self.branches = self.cell = None
+        self.derandomize, self.packet_bytes = bool(derandomize), P // 8
+        zeros = lambda *shape: t.zeros(shape, dtype=t.int32, device=decoder.device)                   # noqa: E731
+        if deinterleave is not None:
+            B, M, nb = int(deinterleave[0]), int(deinterleave[1]), self.packet_bytes
+            if self.drop_bits or pad is not None or P % 8 or B < 2 or M < 1 or nb % B or (rs is not None and self.rs_interleave != 1):
+                raise ValueError("deinterleave=(B, M) needs frames=True, frame_drop_bits=0, no frame_pad, period = 8 n with n a multiple of B, "
+                                 "and with rs= rs_interleave=1 and rs.n == n")
+            H = -(-(B - 1) * M * B // nb)
+            if (H + 1) * nb > 32768:
+                raise ValueError("deinterleave=(B, M): (H + 1) * n is above 32768 (vit_hip_deinterleave_batch)")
+            if derandomize and nb < 188:
+                raise ValueError("dvb_derandomize=True needs packets of at least 188 bytes")
+            self.branches, self.cell = B, M
+            # history, fill and group phase of every stream: a call reads one triple and writes the other
+            self.delay, self.delay_next = ((t.zeros((n, H * nb), dtype=t.uint8, device=decoder.device), zeros(n), zeros(n) - 1) for _ in range(2))
+            self.lock = zeros(n, 2)                                   # the (phase, inverted) the last extraction cut at
+        elif derandomize:
+            raise ValueError("dvb_derandomize=True needs deinterleave=(B, M)")
+        # the unfinished frame of every stream and its bits: a call reads one pair and writes the other
+        self.carry, self.carry_next = ((t.zeros((n, (P + 6) // 8), dtype=t.uint8, device=decoder.device), zeros(n)) for _ in range(2))
+        self.done = [[] for _ in range(n)]                            # (frames, marker_errors[, rs_status]) per call, until taken
+
+    def run(self, out, n_bits, phase0, lock):
+        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted, bit 0 at phase phase0; lock [n_streams][4]: that of the totals so far"""
+        t, dec = self.decoder.torch, self.decoder
+        cap = dec.frames_capacity(n_bits, self.period)
+        fresh = (t.empty((self.n_streams, cap, self.frame_bytes), dtype=t.uint8, device=dec.device),
+                 t.empty(self.n_streams, dtype=t.int32, device=dec.device), t.empty((self.n_streams, cap), dtype=t.int32, device=dec.device))
+        carry, carry_bits = self.carry
+        frames, n, errors, _, _ = dec.frames_extract(out, n_bits, self.period, phase0, lock, carry, carry_bits, self.marker, self.marker_bits,
+                                                     self.drop_bits, self.pad, out=fresh + self.carry_next)
+        self.carry, self.carry_next = self.carry_next, self.carry
+        status, n_errors = None, n                                # `errors` holds one entry per frame extracted ...
+        if self.branches is not None:
+            frames, n, errors, status = self._dvb(frames, n, errors, lock[:, :2])
+            if self.derandomize:
+                n_errors = n                                      # ... or, derandomised, one per packet that came out
+        elif self.rs is not None and frames.shape[1]:
+            _, status = dec.rs_decode(self.rs, frames, n, self.rs_interleave)
+        status = None if status is None else status.cpu().numpy()
+        n_errors = n_errors.cpu().numpy()
+        n, frames, errors = n.cpu().numpy(), frames.cpu().numpy(), errors.cpu().numpy().view(np.uint32).astype(np.int64)
+        for i in range(self.n_streams):
+            if n[i] or n_errors[i]:
+                done = (frames[i, :n[i]].copy(), errors[i, :n_errors[i]].copy())
+                self.done[i].append(done if status is None else done + (status[i, :n[i]].copy(),))
+
+    def _dvb(self, frames, n, errors, lock):
+        """the packets one extraction wrote at `lock` [n_streams][2] -> de-interleaved, Reed-Solomon decoded in place, derandomised:
+        (packets, their number per stream, sync_errors -- or the marker_errors as they came --, rs_status or None), all on the device"""
+        t, dec = self.decoder.torch, self.decoder
+        changed = (lock != self.lock).any(dim=1)
+        self.lock = lock.clone()
+        hist, fill, phase = self.delay
+        hist_out, fill_out, phase_out = self.delay_next
+        self.delay, self.delay_next = self.delay_next, self.delay
+        fill = t.where(changed, t.zeros_like(fill), fill)
+        phase = t.where(changed, t.full_like(phase, -1), phase)
+        out, n_out, _, _ = dec.deinterleave(frames, n, self.branches, self.cell, hist, fill,
+                                            out=(t.empty_like(frames), t.empty(self.n_streams, dtype=t.int32, device=dec.device), hist_out, fill_out))
+        status = None
+        if self.rs is not None:
+            _, status = dec.rs_decode(self.rs, out, n_out, 1)
+        if self.derandomize:
+            out, _, errors = dec.dvb_derandomize(out, n_out, phase, status, phase_out=phase_out)
+        return out, n_out, errors, status
+
+    def take(self):
+        """per stream what came out since the last take, in order; see MultiStreamDecoder.take_frames"""
+        empty = (np.zeros((0, 188 if self.derandomize else self.frame_bytes), dtype=np.uint8), np.zeros(0, dtype=np.int64))
+        if self.rs is not None:
+            empty += (np.zeros((0, self.rs_interleave), dtype=np.int32),)
+        taken = [tuple(np.concatenate(part) for part in zip(*done)) if done else empty for done in self.done]
+        self.done = [[] for _ in range(self.n_streams)]
+        return taken
 
 
 class MultiStreamDecoder:
@@ -77,12 +179,11 @@ class MultiStreamDecoder:
                  channel_errors: bool = False, marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0,
                  frame_pad=None, rs=None, rs_interleave: int = 1, deinterleave=None, dvb_derandomize: bool = False):
         self.decoder = decoder
-        self.n_streams = int(n_streams)
+        self.n_streams = n = int(n_streams)
         self.window, self.head, self.tail, _ = decoder._stream_args(window, head, tail, True, False)
         seg = self.head + self.window + self.tail
         pitch = -(-seg // self.window) * self.window
-        if self.n_streams < 1 or decoder.streams_workspace_bytes(self.n_streams, pitch, seg, True, False, self.window, self.head,
-                                                                 self.tail) == 0:
+        if n < 1 or decoder.streams_workspace_bytes(n, pitch, seg, True, False, self.window, self.head, self.tail) == 0:
             raise ValueError(self._RULE)
         self.n_bits = 0
         self.calls = []                       # (steps, begin, end) of every internal call, for inspection
@@ -90,81 +191,41 @@ class MultiStreamDecoder:
         self._done = False
         self._buf = None                      # device tensor [n_streams][pitch][R], pitch % window == 0
         self._pending = 0                     # steps of it in use, per stream
-        self._carry = np.zeros((self.n_streams, 0), dtype=np.uint8)
-        self._totals = None                   # (errors, compared) per stream when they are kept
+        self._carry = np.zeros((n, 0), dtype=np.uint8)
+        self._errors = self._compared = None  # the channel error totals per stream, when they are kept
         if channel_errors:
-            self._totals = (np.zeros(self.n_streams, dtype=np.int64), np.zeros(self.n_streams, dtype=np.int64))
-            self._state = np.zeros(self.n_streams, dtype=np.int64)    # the last K-1 emitted bits, as a decoder state
-        self._marker = None
+            self._errors, self._compared = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+            self._state = np.zeros(n, dtype=np.int64)                 # the last K-1 emitted bits, as a decoder state
+        self._marker = self._marker_bits = self._period = None
         if marker is not None:
             value, bits = int(marker[0]), int(marker[1])
             if period is None or not 1 <= int(period) < 1 << 31 or not 1 <= bits <= 64 or value >> bits:
                 raise ValueError("marker=(value, bits) needs 1 <= bits <= 64, no bit of value above them, and period=P >= 1")
             t = decoder.torch
-            self._marker = (value, bits, int(period))
-            self._marker_out = (t.zeros((self.n_streams, int(period)), dtype=t.int32, device=decoder.device),
-                                t.zeros((self.n_streams, int(period)), dtype=t.int32, device=decoder.device),
-                                t.zeros((self.n_streams, 4), dtype=t.int32, device=decoder.device))
+            self._marker, self._marker_bits, self._period = value, bits, int(period)
+            # the running totals per phase and the lock they name, on the device
+            self._distance, self._count = (t.zeros((n, int(period)), dtype=t.int32, device=decoder.device) for _ in range(2))
+            self._lock = t.zeros((n, 4), dtype=t.int32, device=decoder.device)
             self._emitted = 0                                         # bits the internal calls have emitted, per stream
-            self._recent = np.zeros((self.n_streams, 0), dtype=np.uint8)    # the last bits-1 of them
-        self._frames = None
-        if frames:
-            if self._marker is None or not 8 <= int(period) or not 0 <= int(frame_drop_bits) < int(period) or self._marker[1] > int(period):
-                raise ValueError("frames=True needs marker=(value, bits), period=P >= max(8, bits) and 0 <= frame_drop_bits < P")
-            t, P, n = decoder.torch, int(period), self.n_streams
-            qb = (P - int(frame_drop_bits) + 7) // 8
-            pad = None
-            if frame_pad is not None:
-                pad = frame_pad if t.is_tensor(frame_pad) else t.from_numpy(np.frombuffer(bytes(frame_pad), dtype=np.uint8).copy())
-                pad = pad.to(device=decoder.device, dtype=t.uint8).reshape(-1).contiguous()
-                if pad.numel() < qb:
-                    raise ValueError(f"frame_pad must hold ceil((period - frame_drop_bits) / 8) = {qb} bytes")
-            self._frames = (int(frame_drop_bits), qb, pad)
-            # the unfinished frame of every stream, ping-ponged: a call reads one pair and writes the other
-            self._frame_carry = [(t.zeros((n, (P + 6) // 8), dtype=t.uint8, device=decoder.device),
-                                  t.zeros(n, dtype=t.int32, device=decoder.device)) for _ in range(2)]
-            self._frame_turn = 0
-            self._frames_done = [[] for _ in range(n)]                # (frames, marker_errors[, rs_status]) per call, until taken
-        self._rs = None
-        if rs is not None:
-            if self._frames is None or int(rs_interleave) < 1 or (int(period) - int(frame_drop_bits)) != 8 * rs.n * int(rs_interleave):
-                raise ValueError("rs= needs frames=True and (period - frame_drop_bits) / 8 == rs.n * rs_interleave")
-            self._rs = (rs, int(rs_interleave))
-        self._dvb = None
-        if deinterleave is not None:
-            B, M = int(deinterleave[0]), int(deinterleave[1])
-            if (self._frames is None or int(frame_drop_bits) != 0 or frame_pad is not None or int(period) % 8 or B < 2 or M < 1
-                    or (int(period) // 8) % B or (self._rs is not None and self._rs[1] != 1)):
-                raise ValueError("deinterleave=(B, M) needs frames=True, frame_drop_bits=0, no frame_pad, period = 8 n with n a multiple of B, "
-                                 "and with rs= rs_interleave=1 and rs.n == n")
-            t, nb, n = decoder.torch, int(period) // 8, self.n_streams
-            H = -(-(B - 1) * M * B // nb)
-            if (H + 1) * nb > 32768:
-                raise ValueError("deinterleave=(B, M): (H + 1) * n is above 32768 (vit_hip_deinterleave_batch)")
-            if dvb_derandomize and nb < 188:
-                raise ValueError("dvb_derandomize=True needs packets of at least 188 bytes")
-            self._dvb = (B, M, bool(dvb_derandomize), nb)
-            # history, fill and group phase of every stream, ping-ponged; the (phase, inverted) the last extraction cut at
-            self._dvb_state = [(t.zeros((n, H * nb), dtype=t.uint8, device=decoder.device), t.zeros(n, dtype=t.int32, device=decoder.device),
-                                t.full((n,), -1, dtype=t.int32, device=decoder.device)) for _ in range(2)]
-            self._dvb_turn = 0
-            self._dvb_lock = t.zeros((n, 2), dtype=t.int32, device=decoder.device)
-        elif dvb_derandomize:
-            raise ValueError("dvb_derandomize=True needs deinterleave=(B, M)")
+            self._recent = np.zeros((n, 0), dtype=np.uint8)           # the last bits-1 of them
+        self._chain = None
+        if frames or rs is not None or deinterleave is not None or dvb_derandomize:
+            self._chain = _FrameChain(decoder, n, frames, self._marker, self._marker_bits, period, frame_drop_bits, frame_pad, rs, rs_interleave,
+                                      deinterleave, dvb_derandomize)
 
     @property
     def channel_errors(self):
-        if self._totals is None:
+        if self._errors is None:
             raise AttributeError("this receiver was made without channel_errors=True")
-        return self._totals
+        return self._errors, self._compared
 
-    def _count(self, out, n_bits, end):
-        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted, from the segment's first emitted step on"""
+    def _count(self, out, bits, n_bits, end):
+        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted (`bits`, unpacked), from the segment's first emitted step on"""
         dec = self.decoder
         err, cmp = dec.channel_errors(self._buf[:, 0 if self._first else self.head:], out, n_bits, tail=end, start_state=self._state,
                                       symbol_frame_stride=self._buf.shape[1] * dec.R)
-        self._totals = (self._totals[0] + err.cpu().numpy(), self._totals[1] + cmp.cpu().numpy())
-        self._state = _next_states(self._state, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits], dec.K)
+        self._errors, self._compared = self._errors + err.cpu().numpy(), self._compared + cmp.cpu().numpy()
+        self._state = _next_states(self._state, bits, dec.K)
 
     def _no_marker(self):
         if self._marker is None:
@@ -173,75 +234,24 @@ class MultiStreamDecoder:
     @property
     def marker_totals(self):
         self._no_marker()
-        return tuple(x.cpu().numpy().view(np.uint32).astype(np.int64) for x in self._marker_out[:2])
+        return tuple(x.cpu().numpy().view(np.uint32).astype(np.int64) for x in (self._distance, self._count))
 
     @property
     def marker_lock(self):
         self._no_marker()
-        return [tuple(int(v) for v in row) for row in self._marker_out[2].cpu().numpy().view(np.uint32)]
+        return [tuple(int(v) for v in row) for row in self._lock.cpu().numpy().view(np.uint32)]
 
-    def _search(self, out, n_bits):
-        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted; the history is what was emitted before them"""
-        value, m, P = self._marker
+    def _search(self, out, bits, n_bits):
+        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted (`bits`, unpacked); the history is what was emitted before them"""
+        m, P = self._marker_bits, self._period
         hb = self._recent.shape[1]
         if n_bits + hb >= m:
             history = [int("".join(map(str, row)), 2) if hb else 0 for row in self._recent]
-            self.decoder.marker_search(out, n_bits, value, m, P, self._emitted % P, history, hb, out=self._marker_out, accumulate=True)
-        bits = np.concatenate([self._recent, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
+            self.decoder.marker_search(out, n_bits, self._marker, m, P, self._emitted % P, history, hb,
+                                       out=(self._distance, self._count, self._lock), accumulate=True)
+        bits = np.concatenate([self._recent, bits], axis=1)
         self._recent = bits[:, max(bits.shape[1] - (m - 1), 0):]
         self._emitted += n_bits
-
-    def _extract(self, out, n_bits, phase0):
-        """out [n_streams][ceil(n_bits/8)]: the bits the call emitted, bit 0 at phase phase0; the lock is that of the totals so far"""
-        value, m, P = self._marker
-        drop, qb, pad = self._frames
-        carry, carry_bits = self._frame_carry[self._frame_turn]
-        carry_out, carry_bits_out = self._frame_carry[1 - self._frame_turn]
-        frames, n, errors, _, _ = self.decoder.frames_extract(out, n_bits, P, phase0, self._marker_out[2], carry, carry_bits, value, m, drop,
-                                                              pad, out=self._frame_out(n_bits) + (carry_out, carry_bits_out))
-        self._frame_turn = 1 - self._frame_turn
-        status, n_errors = None, n                                # `errors` holds one entry per frame extracted ...
-        if self._dvb is not None:
-            frames, n, errors, status = self._dvb_chain(frames, n, errors)
-            if self._dvb[2]:
-                n_errors = n                                      # ... or, derandomised, one per packet that came out
-        elif self._rs is not None and frames.shape[1]:
-            _, status = self.decoder.rs_decode(self._rs[0], frames, n, self._rs[1])
-        status = None if status is None else status.cpu().numpy()
-        n_errors = n_errors.cpu().numpy()
-        n, frames, errors = n.cpu().numpy(), frames.cpu().numpy(), errors.cpu().numpy().view(np.uint32).astype(np.int64)
-        for i in range(self.n_streams):
-            if n[i] or n_errors[i]:
-                done = (frames[i, :n[i]].copy(), errors[i, :n_errors[i]].copy())
-                self._frames_done[i].append(done if status is None else done + (status[i, :n[i]].copy(),))
-
-    def _dvb_chain(self, frames, n, errors):
-        """the packets one extraction wrote -> de-interleaved, Reed-Solomon decoded in place, derandomised: (packets, their number per
-        stream, sync_errors -- or the marker_errors as they came --, rs_status or None), all on the device"""
-        t, dec = self.decoder.torch, self.decoder
-        B, M, derandomize, nb = self._dvb
-        lock = self._marker_out[2][:, :2]
-        changed = (lock != self._dvb_lock).any(dim=1)
-        self._dvb_lock = lock.clone()
-        hist, fill, phase = self._dvb_state[self._dvb_turn]
-        hist_out, fill_out, phase_out = self._dvb_state[1 - self._dvb_turn]
-        self._dvb_turn = 1 - self._dvb_turn
-        fill = t.where(changed, t.zeros_like(fill), fill)
-        phase = t.where(changed, t.full_like(phase, -1), phase)
-        out, n_out, _, _ = dec.deinterleave(frames, n, B, M, hist, fill,
-                                            out=(t.empty_like(frames), t.empty(self.n_streams, dtype=t.int32, device=dec.device), hist_out, fill_out))
-        status = None
-        if self._rs is not None:
-            _, status = dec.rs_decode(self._rs[0], out, n_out, 1)
-        if derandomize:
-            out, _, errors = dec.dvb_derandomize(out, n_out, phase, status, phase_out=phase_out)
-        return out, n_out, errors, status
-
-    def _frame_out(self, n_bits):
-        t, dec = self.decoder.torch, self.decoder
-        cap = dec.frames_capacity(n_bits, self._marker[2])
-        return (t.empty((self.n_streams, cap, self._frames[1]), dtype=t.uint8, device=dec.device),
-                t.empty(self.n_streams, dtype=t.int32, device=dec.device), t.empty((self.n_streams, cap), dtype=t.int32, device=dec.device))
 
     def take_frames(self) -> list:
         """per stream (frames uint8 [n][ceil(Q/8)], marker_errors int64 [n]) -- with rs= also rs_status int32 [n][I] --: the frames
@@ -253,25 +263,16 @@ class MultiStreamDecoder:
         packets, uint8 [k][188], by the rule of vit_hip_dvb_derandomize_batch, and the second their sync_errors, int64 [k]: the bits the
         sync byte differed in from 0x47, or from 0xB8 at the head of a group of eight.  rs_status, int32 [k][1], is there exactly with
         rs=."""
-        if self._frames is None:
+        if self._chain is None:
             raise AttributeError("this receiver was made without frames=True")
-        width = 188 if self._dvb is not None and self._dvb[2] else self._frames[1]
-        empty = (np.zeros((0, width), dtype=np.uint8), np.zeros(0, dtype=np.int64))
-        if self._rs is not None:
-            empty += (np.zeros((0, self._rs[1]), dtype=np.int32),)
-        taken = []
-        for done in self._frames_done:
-            taken.append(tuple(np.concatenate(part) for part in zip(*done)) if done else empty)
-        self._frames_done = [[] for _ in range(self.n_streams)]
-        return taken
+        return self._chain.take()
 
     def _append(self, symbols):
         if symbols is None:
             return
         dec = self.decoder
-        if (symbols.dtype != dec._soft_dtype or not symbols.is_cuda or symbols.dim() < 2 or symbols.shape[0] != self.n_streams
-                or symbols[0].numel() % dec.R != 0):
-            raise ValueError(f"symbols must be a {dec._soft_dtype} CUDA tensor of {self._SHAPE}")
+        if _args.device(symbols, dec._soft_dtype, "symbols").dim() < 2 or symbols.shape[0] != self.n_streams or symbols[0].numel() % dec.R != 0:
+            raise ValueError(f"symbols must be {self._SHAPE}")
         symbols = symbols.reshape(self.n_streams, -1, dec.R)
         P, n = self._pending, symbols.shape[1]
         if self._buf is None or P + n > self._buf.shape[1]:
@@ -288,16 +289,17 @@ class MultiStreamDecoder:
         """one internal call over the first `steps` pending steps of every stream: the bytes it hands back, per stream"""
         out, n_bits = self.decoder.decode_streams(self._buf, steps, self._first, end, self.window, self.head, self.tail)
         self.calls.append((steps, self._first, end))
-        if self._totals is not None:
-            self._count(out, n_bits, end)
+        bits = np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]       # the one read-back of the emitted bits
+        if self._errors is not None:
+            self._count(out, bits, n_bits, end)
         if self._marker is not None:
-            phase0 = self._emitted % self._marker[2]
-            self._search(out, n_bits)
-            if self._frames is not None and n_bits:
-                self._extract(out, n_bits, phase0)
+            phase0 = self._emitted % self._period
+            self._search(out, bits, n_bits)
+            if self._chain is not None and n_bits:
+                self._chain.run(out, n_bits, phase0, self._lock)
         self._first = False
         # whole bytes only: the rest waits in the carry, which the last call flushes
-        bits = np.concatenate([self._carry, np.unpackbits(out.cpu().numpy(), axis=1)[:, :n_bits]], axis=1)
+        bits = np.concatenate([self._carry, bits], axis=1)
         keep = bits.shape[1] if end else bits.shape[1] - bits.shape[1] % 8
         self._carry = bits[:, keep:]
         self.n_bits += keep
@@ -343,8 +345,9 @@ class StreamDecoder(MultiStreamDecoder):
     def __init__(self, decoder: BatchDecoder, window: int = None, head: int = None, tail: int = None, channel_errors: bool = False,
                  marker=None, period: int = None, frames: bool = False, frame_drop_bits: int = 0, frame_pad=None, rs=None,
                  rs_interleave: int = 1, deinterleave=None, dvb_derandomize: bool = False):
-        super().__init__(decoder, 1, window, head, tail, channel_errors, marker, period, frames, frame_drop_bits, frame_pad, rs,
-                         rs_interleave, deinterleave, dvb_derandomize)
+        super().__init__(decoder, 1, window=window, head=head, tail=tail, channel_errors=channel_errors, marker=marker, period=period,
+                         frames=frames, frame_drop_bits=frame_drop_bits, frame_pad=frame_pad, rs=rs, rs_interleave=rs_interleave,
+                         deinterleave=deinterleave, dvb_derandomize=dvb_derandomize)
 
     def take_frames(self):
         return super().take_frames()[0]
