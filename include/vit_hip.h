@@ -791,6 +791,45 @@ int vit_hip_dvb_derandomize_batch(vit_hip_handle h, const uint8_t* d_in, size_t 
                                   uint8_t* d_out, size_t out_stride_bytes, uint32_t* d_phase_out, uint32_t* d_sync_errors,
                                   vit_hip_stream_t stream);
 
+/* ---- the frame check: batched CRC of a bit range of every frame, and its syndrome against the transmitted field --------------------
+ * A corrected Reed-Solomon codeword is a valid one, not necessarily the one sent; a tail-biting decode ranks candidates, it does not
+ * accept one.  What decides is the frame's CRC: the CCSDS frame error control field, the CRC-16 behind a DAB FIB, the CRC-16 / CRC-24
+ * of LTE (XORed with the RNTI on PDCCH, the antenna mask on PBCH), the CRC-32 of MPEG-2 PSI.  vit_hip_crc_batch computes it where the
+ * frames already lie.
+ * A code is (width, poly, init, xorout): 1 <= width <= 32, poly without its x^width term, all three below 2^width.  Rule, bit-exact
+ * and independent of the algorithm, for n data bits, MSB-first, nothing reflected:
+ *   reg = init;  per bit b:  top = (reg >> (width-1)) & 1;  reg = (reg << 1) & (2^width - 1);  if (top ^ b) reg ^= poly;
+ *   crc = reg ^ xorout.
+ * CRC of ASCII "123456789": CCSDS (16, 0x1021, 0xFFFF, 0) 0x29B1; LTE CRC16 (16, 0x1021, 0, 0) 0x31C3; DAB (16, 0x1021, 0xFFFF, 0xFFFF)
+ * 0xD64E; LTE CRC24A (24, 0x864CFB, 0, 0) 0xCDE703; CRC24B (24, 0x800063, 0, 0) 0x23EF52; CRC8 (8, 0x9B, 0, 0) 0xEA; MPEG-2 (32,
+ * 0x04C11DB7, 0xFFFFFFFF, 0) 0x0376E6E7.
+ *   - input: the layout vit_hip_frames_extract, vit_hip_rs_decode_batch and vit_hip_deinterleave_batch share: frame (r, f) at d_frames +
+ *     (r * max_frames + f) * frame_stride_bytes.  With rows = 1 that is the [F][ceil(L/8)] bytes of vit_hip_decode_tail_biting_batch,
+ *     FIBs at stride 32, or the first 223 I bytes of a 255 I byte Reed-Solomon frame;
+ *   - d_n_frames [rows] on the device, or NULL: all max_frames frames of every row.  Frames f >= d_n_frames[r] are neither read nor
+ *     written, and neither are their entries; a count above max_frames reads as max_frames;
+ *   - data: bits [first_bit, first_bit + n_bits) of the frame, bit t of a frame being bit 7 - t%8 of byte t/8.  n_bits = 0 is legal:
+ *     crc = init ^ xorout;
+ *   - d_crc[r * max_frames + f] (may be NULL) = the CRC of the data;
+ *   - d_syndrome[r * max_frames + f] (may be NULL) = crc ^ field, the field being the `width` bits behind the data, MSB-first: 0 means
+ *     the frame checks; on PDCCH it is the RNTI, on PBCH the antenna mask.  At least one of the two outputs is given;
+ *   - frame_stride_bytes: 0 => exactly ceil((first_bit + n_bits (+ width with d_syndrome)) / 8); a non-zero stride is at least that.
+ *     Of a frame only the bytes that hold data bits, and with d_syndrome field bits, are read.
+ * Whatever the count memory holds, the kernel reads no byte outside the frames it owns and writes only entries of frames f < nf.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, crc or d_frames, both outputs
+ * NULL, a width outside 1 .. 32, poly, init or xorout at or above 2^width, first_bit + n_bits + 32 at or above 2^32 - 1, a stride that is
+ * too small, outputs that overlap each other or the input, more than 2^31 - 1 rows, frames per row or blocks (256 threads; a frame takes
+ * 1 .. 64 of them by its length).  rows = 0 or max_frames = 0 returns VIT_HIP_OK with no work.
+ * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, synchronises nothing, can be
+ * captured into a hipGraph behind vit_hip_rs_decode_batch, and reads the handle only for its device.  There is no object to create:
+ * the constants of the code are a handful of scalars worked out on the host per call, the lookup tables are built in LDS by every block.
+ * Out of scope: reflected CRCs (CRC-32/ISO-HDLC and kin); widths above 32; per-frame lengths or codes in one call; a GPU-side CRC
+ * append; a CRC on the DVB transport-packet route. */
+typedef struct vit_hip_crc_params { uint32_t width, poly, init, xorout; } vit_hip_crc_params;
+int vit_hip_crc_batch(vit_hip_handle h, const vit_hip_crc_params* crc, const uint8_t* d_frames, size_t frame_stride_bytes,
+                      size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t first_bit, size_t n_bits,
+                      uint32_t* d_crc, uint32_t* d_syndrome, vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

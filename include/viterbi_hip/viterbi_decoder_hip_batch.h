@@ -235,6 +235,18 @@ public:
                                             d_out, out_stride_bytes, d_phase_out, d_sync_errors, stream),
               "vit_hip_dvb_derandomize_batch");
     }
+    // The frame check (vit_hip_crc_batch): the CRC `crc` = (width <= 32, poly, init, xorout), not reflected, of bits [first_bit, first_bit +
+    // n_bits) of every frame in the layout above -- the frames rs_decode left, or with rows = 1 the bytes decode_tail_biting wrote.  d_crc
+    // [rows][max_frames] (may be nullptr) receives the CRC, d_syndrome [rows][max_frames] (may be nullptr; one of the two is given) the CRC
+    // XORed with the `width` bits behind the data: 0 where the frame checks, the RNTI on PDCCH.  d_n_frames [rows] (nullptr: all
+    // max_frames) bounds the frames of a row that are touched.
+    void crc_check(const vit_hip_crc_params& crc, const uint8_t* d_frames, size_t rows, size_t max_frames, const uint32_t* d_n_frames,
+                   size_t first_bit, size_t n_bits, uint32_t* d_crc, uint32_t* d_syndrome, size_t frame_stride_bytes = 0,
+                   void* stream = nullptr) {
+        check(vit_hip_crc_batch(m_hip, &crc, d_frames, frame_stride_bytes, rows, max_frames, d_n_frames, first_bit, n_bits, d_crc, d_syndrome,
+                                stream),
+              "vit_hip_crc_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -38,6 +38,7 @@ EXPORTS = [
     "vit_hip_frames_capacity", "vit_hip_frames_extract",
     "vit_hip_rs_create", "vit_hip_rs_destroy", "vit_hip_rs_decode_batch",
     "vit_hip_deinterleave_batch", "vit_hip_dvb_derandomize_batch",
+    "vit_hip_crc_batch",
 ]
 
 
@@ -89,6 +90,11 @@ class VitHipRsParams(C.Structure):
     """vit_hip_rs_params: a Reed-Solomon code over GF(256) as libfec describes one"""
     _fields_ = [("gfpoly", C.c_uint32), ("fcr", C.c_uint32), ("prim", C.c_uint32), ("nroots", C.c_uint32), ("pad", C.c_uint32),
                 ("dual_basis", C.c_uint32)]
+
+
+class VitHipCrcParams(C.Structure):
+    """vit_hip_crc_params: a CRC (not reflected), poly without its x^width term"""
+    _fields_ = [("width", C.c_uint32), ("poly", C.c_uint32), ("init", C.c_uint32), ("xorout", C.c_uint32)]
 
 
 class VitHipError(RuntimeError):
@@ -166,6 +172,7 @@ def load():
     L.vit_hip_rs_decode_batch.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp]
     L.vit_hip_deinterleave_batch.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp]
     L.vit_hip_dvb_derandomize_batch.argtypes = [vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp]
+    L.vit_hip_crc_batch.argtypes = [vp, C.POINTER(VitHipCrcParams), vp, sz, sz, sz, vp, sz, sz, vp, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -19,6 +19,7 @@
 //                    and the decode (kernels_rs.hpp)
 //   vit_dvb.hip      the DVB-S stages on either side of it: the convolutional de-interleaver and the energy-dispersal removal
 //                    (kernels_dvb.hpp)
+//   vit_crc.hip      the frame check behind them: the CRC of a bit range of every frame and its syndrome (kernels_crc.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

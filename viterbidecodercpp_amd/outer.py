@@ -1,6 +1,6 @@
 """The outer chain of a receiver on the GPU, behind the Viterbi decoder: frame marker search, frame extraction, Reed-Solomon decoding,
-the convolutional de-interleaver and DVB-S energy-dispersal removal -- the routes of the C ABI that work on the caller's bytes alone and
-read the handle only for its device (csrc/vit_marker.hip, vit_frames.hip, vit_rs.hip, vit_dvb.hip)."""
+the convolutional de-interleaver, DVB-S energy-dispersal removal and the frame check (CRC) -- the routes of the C ABI that work on the
+caller's bytes alone and read the handle only for its device (csrc/vit_marker.hip, vit_frames.hip, vit_rs.hip, vit_dvb.hip, vit_crc.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -222,3 +222,35 @@ class _OuterChain:
             self._handle._h, _ptr(packets), stride, int(packets.shape[-1]), rows, mf, _ptr(n_frames), _ptr(phase), _ptr(rs_status), _ptr(d_out),
             ostride, _ptr(phase_out), _ptr(sync_errors), self._stream()))
         return d_out, phase_out, sync_errors
+
+    def crc_check(self, code, frames, n_bits: int, first_bit: int = 0, n_frames=None, field: bool = True, crc_out=None, syndrome_out=None):
+        """the frame check (vit_hip_crc_batch): the CRC `code` (a crc.CRCCode: CCSDS_CRC16, LTE_CRC16, DAB_CRC16, LTE_CRC24A, ...) of bits
+        [first_bit, first_bit + n_bits) of every frame of `frames`, uint8 CUDA [rows][max_frames][stride] (or [max_frames][stride]: one
+        row; the bytes decode_tail_biting returns, the frames frames_extract and rs_decode wrote), bit t of a frame being bit 7 - t%8 of
+        byte t/8.  n_frames: int32 CUDA [rows], frames at or behind it are neither read nor written and neither are their entries, or
+        None: all.  field=True: the code.width bits behind the data are the transmitted field and the call returns (crc, syndrome),
+        syndrome = crc ^ field: 0 where the frame checks, the RNTI on PDCCH, the antenna mask on PBCH; a frame must hold first_bit +
+        n_bits + width bits.  field=False: returns crc alone, and a frame need only hold the data.  Both are int32 CUDA tensors of the
+        shape frames.shape[:-1] that hold the uint32 values of the ABI (a width-32 value with its top bit set reads negative:
+        .view(torch.uint32), or & 0xFFFFFFFF on an int64 copy); crc_out / syndrome_out reuse such tensors.  Nothing is copied to the
+        host."""
+        t = self.torch
+        n_bits, first_bit = int(n_bits), int(first_bit)
+        if n_bits < 0 or first_bit < 0:
+            raise ValueError("n_bits and first_bit must not be negative")
+        if syndrome_out is not None and not field:
+            raise ValueError("syndrome_out needs field=True")
+        rows, mf, stride = _args.packets(frames, "frames", (first_bit + n_bits + (code.width if field else 0) + 7) // 8)
+        _args.counts(n_frames, rows, "n_frames")
+        shape = tuple(frames.shape[:-1])
+        crc = self._empty(shape, t.int32) if crc_out is None else _args.dense(crc_out, t.int32, rows * mf, "crc_out")
+        syndrome = None
+        if field:
+            syndrome = self._empty(shape, t.int32) if syndrome_out is None else _args.dense(syndrome_out, t.int32, rows * mf, "syndrome_out")
+        params = _lib.VitHipCrcParams(code.width, code.poly, code.init, code.xorout)
+        at = _ptr(frames)
+        if frames.numel() == 0 and rows * mf:                      # frames of no bytes (n_bits = 0, field=False): where they would start
+            at = C.c_void_p(frames.untyped_storage().data_ptr() + frames.storage_offset())
+        _lib.check(_lib.load().vit_hip_crc_batch(self._handle._h, C.byref(params), at, stride, rows, mf, _ptr(n_frames), first_bit,
+                                                 n_bits, _ptr(crc), _ptr(syndrome), self._stream()))
+        return (crc, syndrome) if field else crc

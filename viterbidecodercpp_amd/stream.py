@@ -64,7 +64,17 @@ class _FrameChain:
             raise ValueError("dvb_derandomize=True needs deinterleave=(B, M)")
         # the unfinished frame of every stream and its bits: a call reads one pair and writes the other
         self.carry, self.carry_next = ((t.zeros((n, (P + 6) // 8), dtype=t.uint8, device=decoder.device), zeros(n)) for _ in range(2))
-        self.done = [[] for _ in range(n)]                            # (frames, marker_errors[, rs_status]) per call, until taken
+        self.done = [[] for _ in range(n)]                            # (frames, marker_errors[, rs_status][, crc_syndrome]) per call, until taken
+        self.crc = None                                               # (CRCCode, n_bits, first_bit) once frame_crc() has asked for the check
+
+    def check_crc(self, code, n_bits, first_bit):
+        """MultiStreamDecoder.frame_crc: the frame check behind rs_decode (behind the extraction without rs=) from the next call on"""
+        n_bits, first_bit = int(n_bits), int(first_bit)
+        if self.branches is not None or self.derandomize:
+            raise ValueError("frame_crc: transport packets (deinterleave=, dvb_derandomize=) carry no frame CRC")
+        if n_bits < 0 or first_bit < 0 or first_bit + n_bits + code.width > self.period - self.drop_bits:
+            raise ValueError(f"frame_crc: first_bit + n_bits + width exceeds the {self.period - self.drop_bits} bits of a frame")
+        self.crc = (code, n_bits, first_bit)
 
     def run(self, out, n_bits, phase0, lock):
         """out [n_streams][ceil(n_bits/8)]: the bits the call emitted, bit 0 at phase phase0; lock [n_streams][4]: that of the totals so far"""
@@ -83,13 +93,20 @@ class _FrameChain:
                 n_errors = n                                      # ... or, derandomised, one per packet that came out
         elif self.rs is not None and frames.shape[1]:
             _, status = dec.rs_decode(self.rs, frames, n, self.rs_interleave)
+        syndrome = None
+        if self.crc is not None:
+            syndrome = t.zeros(tuple(frames.shape[:2]), dtype=t.int32, device=dec.device)
+            if frames.shape[1]:
+                dec.crc_check(self.crc[0], frames, self.crc[1], self.crc[2], n, syndrome_out=syndrome)
+            syndrome = syndrome.cpu().numpy().view(np.uint32).astype(np.int64)
         status = None if status is None else status.cpu().numpy()
         n_errors = n_errors.cpu().numpy()
         n, frames, errors = n.cpu().numpy(), frames.cpu().numpy(), errors.cpu().numpy().view(np.uint32).astype(np.int64)
         for i in range(self.n_streams):
             if n[i] or n_errors[i]:
                 done = (frames[i, :n[i]].copy(), errors[i, :n_errors[i]].copy())
-                self.done[i].append(done if status is None else done + (status[i, :n[i]].copy(),))
+                done = done if status is None else done + (status[i, :n[i]].copy(),)
+                self.done[i].append(done if syndrome is None else done + (syndrome[i, :n[i]].copy(),))
 
     def _dvb(self, frames, n, errors, lock):
         """the packets one extraction wrote at `lock` [n_streams][2] -> de-interleaved, Reed-Solomon decoded in place, derandomised:
@@ -116,6 +133,8 @@ class _FrameChain:
         empty = (np.zeros((0, 188 if self.derandomize else self.frame_bytes), dtype=np.uint8), np.zeros(0, dtype=np.int64))
         if self.rs is not None:
             empty += (np.zeros((0, self.rs_interleave), dtype=np.int32),)
+        if self.crc is not None:
+            empty += (np.zeros(0, dtype=np.int64),)
         taken = [tuple(np.concatenate(part) for part in zip(*done)) if done else empty for done in self.done]
         self.done = [[] for _ in range(self.n_streams)]
         return taken
@@ -262,10 +281,24 @@ class MultiStreamDecoder:
         >= k (the packets that fill the delay lines are counted too).  With dvb_derandomize=True the first element is the transport
         packets, uint8 [k][188], by the rule of vit_hip_dvb_derandomize_batch, and the second their sync_errors, int64 [k]: the bits the
         sync byte differed in from 0x47, or from 0xB8 at the head of a group of eight.  rs_status, int32 [k][1], is there exactly with
-        rs=."""
+        rs=.  After frame_crc() one further, last element: crc_syndrome int64 [n] (see there)."""
         if self._chain is None:
             raise AttributeError("this receiver was made without frames=True")
         return self._chain.take()
+
+    def frame_crc(self, code, n_bits: int, first_bit: int = 0):
+        """the frame check on the device (BatchDecoder.crc_check), asked for before the first push: `code` is a crc.CRCCode
+        (CCSDS_CRC16: the frame error control field), the data are bits [first_bit, first_bit + n_bits) of every frame as take_frames()
+        returns it, the transmitted field the code.width bits behind them.  Every internal call then runs the check right behind
+        rs_decode (corrected frames are checked; without rs= behind the extraction), and take_frames() returns one further, last element
+        per stream: crc_syndrome int64 [n] = crc ^ field, 0 where the frame checks.  rs_status >= 0 says a codeword is valid, not that
+        it is the one sent: this is what tells.  ValueError after a push, without frames=True, with deinterleave= or dvb_derandomize=
+        (transport packets carry no frame CRC), and when first_bit + n_bits + width exceeds the frame."""
+        if self.calls or self._buf is not None or self._done:
+            raise ValueError("frame_crc must be called before the first push")
+        if self._chain is None:
+            raise ValueError("frame_crc needs frames=True")
+        self._chain.check_crc(code, n_bits, first_bit)
 
     def _append(self, symbols):
         if symbols is None:
