@@ -830,6 +830,44 @@ int vit_hip_crc_batch(vit_hip_handle h, const vit_hip_crc_params* crc, const uin
                       size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t first_bit, size_t n_bits,
                       uint32_t* d_crc, uint32_t* d_syndrome, vit_hip_stream_t stream);
 
+/* ---- LTE rate de-matching: from the demodulator's soft bits to the symbols the tail-biting decode reads --------------------------
+ * PBCH and PDCCH send the K = 7, R = 1/3 tail-biting code through the rate matching of 3GPP TS 36.212 5.1.4.2 and a Gold-sequence
+ * scrambler: 120 coded PBCH bits go out as 1920 (16 repetitions that must be ADDED), the 129 of a 43-bit PDCCH candidate as 72, 144, 288
+ * or 576.  vit_hip_lte_rate_dematch_batch descrambles, adds the repetitions and writes the [frames][D][3] symbols
+ * vit_hip_decode_tail_biting_batch takes, 0 (the erasure of vit_hip_depuncture_batch and vit_hip_channel_errors_batch) where nothing
+ * was sent.  The rule is integer-exact and independent of the algorithm.
+ * Transmit side, for each coded stream d(i)[0 .. D), i = 0, 1, 2 the polynomial index (the last axis of [D][3]): Rsb = ceil(D / 32),
+ * Kpi = 32 Rsb, N_D = Kpi - D; y = N_D NULLs followed by d(i), written row by row into Rsb x 32; the columns permuted with the pattern of
+ * the convolutional code (table 5.1.4-2), P = <1,17,9,25,5,21,13,29,3,19,11,27,7,23,15,31,0,16,8,24,4,20,12,28,2,18,10,26,6,22,14,30>, and
+ * read column by column: v(i)[c Rsb + r] = y[P[c] + 32 r].  The circular buffer is w = v(0) | v(1) | v(2); e[k] is the k-th non-NULL
+ * entry met walking w cyclically from 0: e[k] = w_nonnull[k mod 3D].  map[j], j in [0, 3D), is the decoder-order index q = 3 d + i of
+ * the j-th non-NULL entry (D = 32: stream 0 of the map reads d = P; D = 33: 2,18,10,26,6,22,14,30,4,20,12,28,8,24,16,0,32,1,17,...).
+ * Receive side, for frame f and output position q:
+ *   out[f][q] = clamp(round_shift(sum over k < E_f with map[k mod 3D] = q of s(f,k) * received[base_f + k])),
+ * summed in int32 (modulo 2^32), round_shift(x) = (x + ((1 << shift) >> 1)) >> shift (arithmetic), clamp to [clamp_lo, clamp_hi]; an
+ * output without a contribution is 0 (through the same clamp).
+ *   - base_f = d_offset ? d_offset[f] : f * received_frame_stride, in elements; E_f = min(d_count ? d_count[f] : E_max, E_max), cut
+ *     further so that base_f + E_f <= n_received, 0 where base_f >= n_received.  Whatever the count and offset memory holds, nothing
+ *     outside d_received[0 .. n_received) is read.  Every frame's 3D outputs are always written;
+ *   - s(f,k) = -1 where d_scramble is given and its bit g' = (base_f + k) mod scramble_period (scramble_period = 0: g' = base_f + k)
+ *     is set, bit t being bit 7 - t%8 of byte t/8; else +1.  The negation is int32: -(-128) is 128.  The mask holds scramble_period
+ *     bits (0: n_received).  Frames at stride E with period E share one mask; offsets into one control region with period 0 use the
+ *     region's.
+ * soft_t is the handle's symbol type; its code rate must be 1/3.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the output untouched, for a NULL handle, d_received or d_symbols_out, a
+ * handle with R != 3, D = 0 or D > 8192, E_max = 0 or E_max >= 2^24, n_received >= 2^32, shift > 15, clamp_lo > clamp_hi or either outside
+ * soft_t, without d_offset a stride below E_max or (frames - 1) * stride + E_max > n_received, an output that overlaps the input (or
+ * d_offset / d_count), frames * 3 D >= 2^32, d_received or d_symbols_out not aligned to soft_t.  frames = 0 returns VIT_HIP_OK with no
+ * work.
+ * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, needs no workspace, synchronises
+ * nothing and can be captured into a hipGraph in front of vit_hip_decode_tail_biting_batch.
+ * Out of scope: turbo-code rate matching (the other permutation, bit selection with k0, soft-buffer limits); PDCCH REG de-interleaving
+ * and the cyclic shift; per-frame D in one call; a GPU rate matcher; UCI / CQI multiplexing on PUSCH; demodulation. */
+int vit_hip_lte_rate_dematch_batch(vit_hip_handle h, const void* d_received, size_t n_received, size_t received_frame_stride,
+                                   const uint32_t* d_offset, const uint32_t* d_count, size_t frames, size_t D, size_t E_max,
+                                   const uint8_t* d_scramble, size_t scramble_period, unsigned shift, int clamp_lo, int clamp_hi,
+                                   void* d_symbols_out /* [frames][D][3] soft_t */, vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

@@ -247,6 +247,19 @@ public:
                                 stream),
               "vit_hip_crc_batch");
     }
+    // LTE rate de-matching (vit_hip_lte_rate_dematch_batch; 3GPP TS 36.212 5.1.4.2 undone) in front of decode_tail_biting: the soft bits
+    // d_received [n_received] -> d_symbols_out [frames][D][3], a decoder of R = 3.  Frame f is the elements [base, base + E) with base =
+    // d_offset ? d_offset[f] : f * received_frame_stride and E = min(d_count ? d_count[f] : E_max, E_max), cut at n_received; the
+    // repetitions of a coded bit are added in int32, negated where the bit (base + k) mod scramble_period (0: base + k) of d_scramble
+    // (MSB-first; nullptr: off) is set, rounded by (x + ((1 << shift) >> 1)) >> shift and clamped to [clamp_lo, clamp_hi]; 0 where
+    // nothing was sent.
+    void lte_rate_dematch(const soft_t* d_received, size_t n_received, size_t received_frame_stride, const uint32_t* d_offset,
+                          const uint32_t* d_count, size_t frames, size_t D, size_t E_max, const uint8_t* d_scramble, size_t scramble_period,
+                          unsigned shift, int clamp_lo, int clamp_hi, soft_t* d_symbols_out, void* stream = nullptr) {
+        check(vit_hip_lte_rate_dematch_batch(m_hip, d_received, n_received, received_frame_stride, d_offset, d_count, frames, D, E_max,
+                                             d_scramble, scramble_period, shift, clamp_lo, clamp_hi, d_symbols_out, stream),
+              "vit_hip_lte_rate_dematch_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -88,3 +88,35 @@ def puncture_map(owner, mask):
         idx = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
         cached = owner._puncture_map = (key, owner.torch.from_numpy(idx).to(owner.device))
     return cached[1]
+
+
+def lte_frames(received, dtype, D, E, offsets, counts):
+    """(n_received, frames, frame stride, E_max) of an lte_rate_dematch call.  Without `offsets`, `received` is [frames][>= E] of `dtype`
+    with contiguous rows (its row stride is the frame stride; one row: [>= E]) and E defaults to the row length; with `offsets`, int32 [F]
+    (the uint32 values of the ABI), it is one contiguous region the offsets point into and E, the most one frame holds, must be given.
+    `counts`: None, or int32 [frames].  The region ends with the tensor: nothing behind its last element is the call's to read"""
+    import torch
+    if not 1 <= int(D) <= 8192:
+        raise ValueError("D must be 1 .. 8192")
+    if offsets is not None:
+        if E is None:
+            raise ValueError("offsets need E, the most elements one frame holds")
+        frames = dense(offsets, torch.int32, None, "offsets").numel()
+        n, stride = dense(received, dtype, None, "received").numel(), 0
+    else:
+        if device(received, dtype, "received").dim() not in (1, 2) or (received.numel() and received.stride(-1) != 1):
+            raise ValueError("received must be [frames][>= E] with contiguous rows (or one frame), or one region with offsets")
+        E = int(received.shape[-1]) if E is None else int(E)
+        if received.shape[-1] < E:
+            raise ValueError(f"received holds {received.shape[-1]} elements per frame, E is {E}")
+        frames = 1 if received.dim() == 1 else int(received.shape[0])
+        stride = int(received.stride(0)) if frames > 1 else E
+        if stride < E:
+            raise ValueError("the frames of received overlap")
+        n = (frames - 1) * stride + E if frames else 0
+    E = int(E)
+    if not 1 <= E < 1 << 24:
+        raise ValueError("E must be 1 .. 2^24 - 1")
+    if counts is not None:
+        dense(counts, torch.int32, frames, "counts")
+    return n, frames, stride, E

@@ -20,6 +20,8 @@
 //   vit_dvb.hip      the DVB-S stages on either side of it: the convolutional de-interleaver and the energy-dispersal removal
 //                    (kernels_dvb.hpp)
 //   vit_crc.hip      the frame check behind them: the CRC of a bit range of every frame and its syndrome (kernels_crc.hpp)
+//   vit_lte.hip      the front of the LTE control-channel route: descrambling and rate de-matching into the symbols the tail-biting
+//                    decode reads (kernels_lte.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

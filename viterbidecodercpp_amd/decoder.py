@@ -590,6 +590,38 @@ class BatchDecoder(_OuterChain):
                                                         frames, _ptr(out), self._stream()))
         return out
 
+    def lte_rate_dematch(self, received, D: int, E: int = None, offsets=None, counts=None, scramble=None, scramble_period: int = 0,
+                         shift: int = 0, clamp=None, out=None):
+        """LTE rate de-matching in front of decode_tail_biting (vit_hip_lte_rate_dematch_batch; 3GPP TS 36.212 5.1.4.2 undone): the
+        demodulator's soft bits -> symbols [F][D][3], the repetitions of a coded bit added in int32, rounded by `shift` ((x + ((1 <<
+        shift) >> 1)) >> shift) and clamped to `clamp` = (low, high), default the decoder's soft_decision_low / high; 0 where nothing
+        was sent.  received: [F][>= E] of the decoder's symbol dtype, frame f in row f (E defaults to the row length), or with
+        `offsets` (int32 CUDA [F]: element offsets, odd and overlapping ones included) one contiguous region of which nothing behind
+        its end is read.  counts: int32 CUDA [F], the elements of each frame (cut at E), or None: E.  scramble: uint8 CUDA, the mask
+        packed MSB-first (lte.lte_gold_sequence); the bit of region element g is g mod scramble_period (0: g) -- frames in rows of E
+        with scramble_period=E share one mask.  The rule on the host: lte.lte_rate_dematch_numpy.  A decoder of rate 1/3 only.
+        Nothing is copied to the host."""
+        t = self.torch
+        D, shift, period = int(D), int(shift), int(scramble_period)
+        n, frames, stride, E = _args.lte_frames(received, self._soft_dtype, D, E, offsets, counts)
+        if self.R != 3:
+            raise ValueError("LTE rate de-matching feeds a rate 1/3 decoder")
+        i = self._handle.info
+        lo, hi = (i.soft_decision_low, i.soft_decision_high) if clamp is None else (int(clamp[0]), int(clamp[1]))
+        if not 0 <= shift <= 15 or lo > hi or period < 0:
+            raise ValueError("shift must be 0 .. 15, clamp = (low, high) with low <= high, scramble_period not negative")
+        if scramble is not None and _args.dense(scramble, t.uint8, None, "scramble").numel() * 8 < (period or n):
+            raise ValueError(f"scramble must hold {period or n} bits")
+        if out is None:
+            out = self._empty((frames, D, 3), self._soft_dtype)
+        _args.dense(out, self._soft_dtype, frames * D * 3, "out")
+        if frames == 0:
+            return out
+        _lib.check(_lib.load().vit_hip_lte_rate_dematch_batch(
+            self._handle._h, _ptr(received), n, stride, _ptr(offsets), _ptr(counts), frames, D, E, _ptr(scramble), period, shift, lo, hi,
+            _ptr(out), self._stream()))
+        return out
+
     def synth(self, frames: int, L: int, ebn0_db, seed: int = 1, first_frame: int = 0, tx_out=None, symbols_out=None):
         """synthetic AWGN frames of this decoder's code, generated in HBM by one HIP kernel (vit_hip_synth_batch: the
         reference BER harness's generator, examples/run_snr_ber.cpp:311-359).  ebn0_db=None: noise-free symbols at exactly
