@@ -868,6 +868,60 @@ int vit_hip_lte_rate_dematch_batch(vit_hip_handle h, const void* d_received, siz
                                    const uint8_t* d_scramble, size_t scramble_period, unsigned shift, int clamp_lo, int clamp_hi,
                                    void* d_symbols_out /* [frames][D][3] soft_t */, vit_hip_stream_t stream);
 
+/* ---- the DAB receive chain: time de-interleaver and depuncturing in front of the decode, energy dispersal behind it ---------------
+ * ETSI EN 300 401 sends every soft bit of a Main Service Channel sub-channel 0 .. 15 Common Interleaved Frames (24 ms each) late
+ * (clause 12), punctures the K = 7, R = 1/4 mother code with several vectors in sequence (clause 11; the maps are built by the host
+ * layer: dab.py) and XORs the x^9 + x^5 + 1 sequence, restarted every logical frame, onto the bits (clause 10).
+ *
+ * vit_hip_dab_deinterleave_batch: bit-exact and independent of the algorithm; soft_t is the handle's symbol type and values pass through
+ * unchanged.  d(j) is the 4-bit reversal of j (0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15), H = 15.  Per row r:
+ *   - input: received frame (r, f) is n_received soft bits at d_in + r * in_row_stride + f * in_frame_stride, in elements of soft_t
+ *     (in_frame_stride = 0 => n_received, in_row_stride = 0 => max_frames * frame stride; non-zero strides are at least those: with a
+ *     frame stride of 55296 a sub-channel is read in place out of whole CIFs).  nf = min(d_n_frames[r], max_frames); d_n_frames == NULL:
+ *     all max_frames frames;
+ *   - history, as vit_hip_deinterleave_batch: row r of d_hist_in starts at r * hist_row_stride elements (0 => H * n_received; in and out
+ *     alike) and holds H frames of n_received, packed, the newest last, of which the last fill = min(d_fill_in[r], H) are real.
+ *     d_hist_in == NULL: every fill = 0 and d_fill_in is not read.  S is the fill real history frames, then the nf input frames; T =
+ *     fill + nf;
+ *   - output: nout = max(0, T - H), written to d_n_out[r].  The transmitter sent b[r'][i] = a[r' - d(i mod 16)][i], so logical frame k
+ *     is a_k[i] = S[T - nout - H + k + d(i mod 16)][i] = S[k + d(i mod 16)][i] (T - nout = H whenever nout > 0): the frame index never
+ *     exceeds T - 1.  With p = d_source_index[q], output symbol q < symbols_per_frame of frame k < nout is a_k[p] where 0 <= p <
+ *     n_received, else 0, the erasure of vit_hip_depuncture_batch.  d_source_index == NULL is the identity: it requires
+ *     symbols_per_frame == n_received and gives the de-interleaver alone.  Output frame (r, k) lies at d_out + (r * max_frames + k) *
+ *     symbols_per_frame; frames k >= nout are NOT written.  With symbols_per_frame = 4 (L + 6) that is the [frames][L + 6][4] buffer
+ *     vit_hip_decode_batch reads;
+ *   - new history: the last min(H, T) frames of S, right-aligned in row r of d_hist_out; d_fill_out[r] = min(H, T).  The frames of the
+ *     row in front of them are not written.  In and out are distinct buffers the caller ping-pongs.
+ * Whatever the count, fill and map memory holds, nothing outside the buffers is read or written.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_in, d_out, d_n_out, d_hist_out
+ * or d_fill_out, d_hist_in without d_fill_in, n_received = 0 or symbols_per_frame = 0, 16 * n_received or symbols_per_frame at or above
+ * 2^32, a stride that is too small, a NULL map with symbols_per_frame != n_received, d_in, d_out or a history not aligned to soft_t, the
+ * map or a count array not aligned to 4 bytes, d_out overlapping the input, a history or the map, d_hist_out overlapping the input,
+ * d_hist_in or the map, count arrays written that overlap each other or those read, more than 2^31 - 1 rows, frames per row or blocks,
+ * rows * max_frames * symbols_per_frame at or above 2^32.  rows = 0 or max_frames = 0 returns VIT_HIP_OK with no work.
+ *
+ * vit_hip_dab_descramble_batch: p[n] = p[n-5] ^ p[n-9] with p[-9 .. -1] = 1, period 511: 0000 0111 1011 1110 ..., as bytes MSB-first 07
+ * BE 2E 64 12 9D A3 CF.  Bit t < n_bits of every frame f < nf is in ^ p[t mod 511], bit t being bit 7 - t%8 of byte t/8; the bits at or
+ * behind n_bits in the last byte are copied unchanged.  Layout, counts and the "not written" rule are those of vit_hip_crc_batch: frame
+ * (r, f) at (r * max_frames + f) * stride, 0 => ceil(n_bits / 8) (in and out each); frames f >= nf are neither read nor written, and of a
+ * frame only its ceil(n_bits / 8) bytes.  d_out == d_in with equal strides is in place; otherwise the two do not overlap.  Dispersal is
+ * its own inverse.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the output untouched, for a NULL handle, d_in or d_out, n_bits + 32 at or
+ * above 2^32 - 1, a stride that is too small, d_out overlapping d_in otherwise than above or overlapping d_n_frames, more than 2^31 - 1
+ * rows or frames per row, rows * max_frames * (n_bits / 32 + 2) at or above 2^32.  rows = 0, max_frames = 0 or n_bits = 0 returns
+ * VIT_HIP_OK with no work.
+ * Batch calls like the others: each only enqueues ONE kernel on `stream` (no memset), allocates nothing, needs no object, workspace or pad
+ * buffer, synchronises nothing and can be captured into a hipGraph around vit_hip_decode_batch.
+ * Out of scope: the unequal-error-protection profile table (a UEP row is whatever map the caller passes); a fast path for one short
+ * push; the Reed-Solomon code and superframe synchronisation of DAB+; OFDM demodulation and frequency de-interleaving. */
+int vit_hip_dab_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in_row_stride, size_t in_frame_stride, size_t rows,
+                                   size_t max_frames, const uint32_t* d_n_frames, size_t n_received, const int32_t* d_source_index,
+                                   size_t symbols_per_frame, const void* d_hist_in, const uint32_t* d_fill_in, size_t hist_row_stride,
+                                   void* d_out, uint32_t* d_n_out, void* d_hist_out, uint32_t* d_fill_out, vit_hip_stream_t stream);
+int vit_hip_dab_descramble_batch(vit_hip_handle h, const uint8_t* d_in, size_t frame_stride_bytes, size_t rows, size_t max_frames,
+                                 const uint32_t* d_n_frames, size_t n_bits, uint8_t* d_out, size_t out_stride_bytes,
+                                 vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

@@ -260,6 +260,28 @@ public:
                                              d_scramble, scramble_period, shift, clamp_lo, clamp_hi, d_symbols_out, stream),
               "vit_hip_lte_rate_dematch_batch");
     }
+    // The DAB receive chain around decode (vit_hip_dab_deinterleave_batch / vit_hip_dab_descramble_batch; ETSI EN 300 401 clauses 12, 11
+    // and 10).  dab_deinterleave undoes the time interleaver -- soft bit i of a frame was sent bitrev4(i mod 16) frames late -- on rows of
+    // received frames of n_received soft bits (frame (r, f) at d_in + r * in_row_stride + f * in_frame_stride, 0: packed) and depunctures
+    // through d_source_index [symbols_per_frame] (nullptr: the identity) in the same pass: d_out [rows][max_frames][symbols_per_frame]
+    // receives the d_n_out[r] logical frames completed, 0 where the map names nothing.  d_hist_in / d_fill_in (nullptr: none) are the 15
+    // frames the previous call left as d_hist_out / d_fill_out.  dab_descramble XORs the energy-dispersal sequence off the first n_bits
+    // bits of every frame of decoded bytes (frame (r, f) at (r * max_frames + f) * stride, 0: ceil(n_bits / 8)); d_out == d_in is in place.
+    void dab_deinterleave(const soft_t* d_in, size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t n_received,
+                          const int32_t* d_source_index, size_t symbols_per_frame, const soft_t* d_hist_in, const uint32_t* d_fill_in,
+                          soft_t* d_out, uint32_t* d_n_out, soft_t* d_hist_out, uint32_t* d_fill_out, size_t in_row_stride = 0,
+                          size_t in_frame_stride = 0, size_t hist_row_stride = 0, void* stream = nullptr) {
+        check(vit_hip_dab_deinterleave_batch(m_hip, d_in, in_row_stride, in_frame_stride, rows, max_frames, d_n_frames, n_received,
+                                             d_source_index, symbols_per_frame, d_hist_in, d_fill_in, hist_row_stride, d_out, d_n_out,
+                                             d_hist_out, d_fill_out, stream),
+              "vit_hip_dab_deinterleave_batch");
+    }
+    void dab_descramble(const uint8_t* d_in, size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t n_bits, uint8_t* d_out,
+                        size_t frame_stride_bytes = 0, size_t out_stride_bytes = 0, void* stream = nullptr) {
+        check(vit_hip_dab_descramble_batch(m_hip, d_in, frame_stride_bytes, rows, max_frames, d_n_frames, n_bits, d_out, out_stride_bytes,
+                                           stream),
+              "vit_hip_dab_descramble_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -48,23 +48,23 @@ def packets(x, what, least):
     return rows, mf, (int(x.stride(-2)) if mf > 1 or rows > 1 else int(x.shape[-1]))
 
 
-def row_buffer(x, rows, least, what):
-    """the row stride of a uint8 buffer [rows][>= least] with contiguous rows that is carried from call to call; a single row's stride is
-    its width"""
+def row_buffer(x, rows, least, what, dtype=None):
+    """the row stride of a buffer [rows][>= least] of `dtype` (None: uint8) with contiguous rows that is carried from call to call; a
+    single row's stride is its width"""
     import torch
-    if device(x, torch.uint8, what).dim() != 2 or x.shape[0] != rows or x.shape[1] < least or x.stride(1) != 1:
+    if device(x, dtype or torch.uint8, what).dim() != 2 or x.shape[0] != rows or x.shape[1] < least or x.stride(1) != 1:
         raise ValueError(f"{what} must be [{rows}][>= {least}] with contiguous rows")
     return int(x.stride(0)) if rows > 1 else int(x.shape[1])
 
 
-def carried(prev, prev_count, nxt, rows, least, what, counted):
+def carried(prev, prev_count, nxt, rows, least, what, counted, dtype=None):
     """the row stride of the row buffer `nxt` (`what`_out) a call writes and of `prev` (`what`), the one the call before wrote (None:
     nothing carried): `prev` comes with its int32 counts [rows] (`counted`), is another tensor than `nxt` and has its row stride"""
-    stride = row_buffer(nxt, rows, least, f"{what}_out")
+    stride = row_buffer(nxt, rows, least, f"{what}_out", dtype)
     if prev is not None:
         if counts(prev_count, rows, counted) is None:
             raise ValueError(f"{what} needs {counted}, an int32 tensor [{rows}]")
-        if row_buffer(prev, rows, least, what) != stride or prev.data_ptr() == nxt.data_ptr():
+        if row_buffer(prev, rows, least, what, dtype) != stride or prev.data_ptr() == nxt.data_ptr():
             raise ValueError(f"{what} and {what}_out must be distinct tensors with the same row stride")
     return stride
 
@@ -120,3 +120,17 @@ def lte_frames(received, dtype, D, E, offsets, counts):
     if counts is not None:
         dense(counts, torch.int32, frames, "counts")
     return n, frames, stride, E
+
+
+def soft_frames(x, dtype, what, least):
+    """(rows, max_frames, row stride, frame stride), in elements, of a tensor of `dtype` [rows][max_frames][>= least] or [max_frames][...]
+    (one row) whose frames are contiguous, do not overlap and lie in ascending order: a sub-channel cut out of whole CIFs as a view is
+    read in place.  The strides of a single frame or row are never used (0: packed)"""
+    if device(x, dtype, what).dim() not in (2, 3) or (x.numel() and x.stride(-1) != 1) or x.shape[-1] < least:
+        raise ValueError(f"{what} must be [rows][max_frames][>= {least}] or [max_frames][...] with contiguous frames")
+    rows, mf = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2])
+    fs = int(x.stride(-2)) if mf > 1 else 0
+    rs = int(x.stride(0)) if x.dim() == 3 and rows > 1 else 0
+    if (mf > 1 and fs < least) or (rows > 1 and rs < mf * (fs or least)):
+        raise ValueError(f"the frames of {what} overlap")
+    return rows, mf, rs, fs

@@ -40,6 +40,7 @@ EXPORTS = [
     "vit_hip_deinterleave_batch", "vit_hip_dvb_derandomize_batch",
     "vit_hip_crc_batch",
     "vit_hip_lte_rate_dematch_batch",
+    "vit_hip_dab_deinterleave_batch", "vit_hip_dab_descramble_batch",
 ]
 
 
@@ -175,6 +176,8 @@ def load():
     L.vit_hip_dvb_derandomize_batch.argtypes = [vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, sz, vp, vp, vp]
     L.vit_hip_crc_batch.argtypes = [vp, C.POINTER(VitHipCrcParams), vp, sz, sz, sz, vp, sz, sz, vp, vp, vp]
     L.vit_hip_lte_rate_dematch_batch.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, sz, vp, sz, C.c_uint, i32, i32, vp, vp]
+    L.vit_hip_dab_deinterleave_batch.argtypes = [vp, vp, sz, sz, sz, sz, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.vit_hip_dab_descramble_batch.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp, sz, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

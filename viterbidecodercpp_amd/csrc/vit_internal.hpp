@@ -22,6 +22,8 @@
 //   vit_crc.hip      the frame check behind them: the CRC of a bit range of every frame and its syndrome (kernels_crc.hpp)
 //   vit_lte.hip      the front of the LTE control-channel route: descrambling and rate de-matching into the symbols the tail-biting
 //                    decode reads (kernels_lte.hpp)
+//   vit_dab.hip      the DAB receive chain around the decode: time de-interleaver fused with depuncturing in front, energy-dispersal
+//                    removal behind (kernels_dab.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -622,6 +622,40 @@ class BatchDecoder(_OuterChain):
             _ptr(out), self._stream()))
         return out
 
+    def dab_deinterleave(self, frames, n_frames=None, source_index=None, hist=None, fill=None, n_received: int = None, out=None):
+        """the DAB time de-interleaver fused with depuncturing, in front of decode (vit_hip_dab_deinterleave_batch; ETSI EN 300 401
+        clauses 12 and 11).  frames: the received soft bits, a CUDA tensor of the decoder's symbol dtype [rows][max_frames][>= n] (or
+        [max_frames][...]: one row; n = n_received, by default the last dimension) -- a view with larger strides, a sub-channel cut out
+        of whole CIFs, is read in place.  n_frames: int32 CUDA [rows] or None: all.  source_index: int32 CUDA [symbols_per_frame], the
+        received soft bit every output symbol is (dab.DabProfile.source_index(); an entry outside 0 .. n-1 gives 0, the erasure), or
+        None: the identity, the de-interleaver alone.  hist / fill: the [rows][15 n] and int32 [rows] the previous call returned as
+        hist_out / fill_out (None: nothing carried).  returns (out, n_out, hist_out, fill_out): [rows][max_frames][symbols_per_frame]
+        of which the first n_out[r] (int32 [rows]) frames of row r are written -- symbol q of frame k is soft bit p = source_index[q] of
+        frame k + bitrev4(p mod 16) of the real history frames followed by the input --, and the last min(15, all) frames of that
+        sequence with their number.  out = the same four reuses those tensors; hist and hist_out must be distinct and have the same row
+        stride.  The rule on the host: dab.dab_time_deinterleave_numpy and dab.dab_depuncture_numpy.  Nothing is copied to the host."""
+        t = self.torch
+        n = int(frames.shape[-1]) if n_received is None else int(n_received)
+        if n < 1:
+            raise ValueError("n_received must be at least 1")
+        rows, mf, rs, fs = _args.soft_frames(frames, self._soft_dtype, "frames", n)
+        if rows == 0 or mf == 0:
+            raise ValueError("frames holds no frame: a call without input changes nothing")
+        spf = n if source_index is None else _args.dense(source_index, t.int32, None, "source_index").numel()
+        if spf < 1:
+            raise ValueError("source_index must hold at least one entry")
+        if out is None:
+            out = (self._empty((rows, mf, spf), self._soft_dtype), self._empty(rows, t.int32), self._empty((rows, 15 * n), self._soft_dtype),
+                   self._empty(rows, t.int32))
+        d_out, n_out, hist_out, fill_out = out
+        _args.dense(d_out, self._soft_dtype, rows * mf * spf, "out[0]")
+        _args.counts(n_frames, rows, "n_frames"), _args.dense(n_out, t.int32, rows, "out[1]"), _args.dense(fill_out, t.int32, rows, "out[3]")
+        hstride = _args.carried(hist, fill, hist_out, rows, 15 * n, "hist", "fill", self._soft_dtype)
+        _lib.check(_lib.load().vit_hip_dab_deinterleave_batch(
+            self._handle._h, _ptr(frames), rs, fs, rows, mf, _ptr(n_frames), n, _ptr(source_index), spf, _ptr(hist),
+            _ptr(fill) if hist is not None else None, hstride, _ptr(d_out), _ptr(n_out), _ptr(hist_out), _ptr(fill_out), self._stream()))
+        return d_out, n_out, hist_out, fill_out
+
     def synth(self, frames: int, L: int, ebn0_db, seed: int = 1, first_frame: int = 0, tx_out=None, symbols_out=None):
         """synthetic AWGN frames of this decoder's code, generated in HBM by one HIP kernel (vit_hip_synth_batch: the
         reference BER harness's generator, examples/run_snr_ber.cpp:311-359).  ebn0_db=None: noise-free symbols at exactly

@@ -1,6 +1,7 @@
 """The outer chain of a receiver on the GPU, behind the Viterbi decoder: frame marker search, frame extraction, Reed-Solomon decoding,
-the convolutional de-interleaver, DVB-S energy-dispersal removal and the frame check (CRC) -- the routes of the C ABI that work on the
-caller's bytes alone and read the handle only for its device (csrc/vit_marker.hip, vit_frames.hip, vit_rs.hip, vit_dvb.hip, vit_crc.hip)."""
+the convolutional de-interleaver, DVB-S energy-dispersal removal, the frame check (CRC) and DAB energy-dispersal removal -- the routes of the C ABI that work on the
+caller's bytes alone and read the handle only for its device (csrc/vit_marker.hip, vit_frames.hip, vit_rs.hip, vit_dvb.hip, vit_crc.hip,
+vit_dab.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -254,3 +255,32 @@ class _OuterChain:
         _lib.check(_lib.load().vit_hip_crc_batch(self._handle._h, C.byref(params), at, stride, rows, mf, _ptr(n_frames), first_bit,
                                                  n_bits, _ptr(crc), _ptr(syndrome), self._stream()))
         return (crc, syndrome) if field else crc
+
+    def dab_descramble(self, frames, n_bits: int, n_frames=None, out=None, in_place: bool = False):
+        """DAB energy-dispersal removal (vit_hip_dab_descramble_batch; ETSI EN 300 401 clause 10) on `frames`, the uint8 CUDA tensor
+        [rows][max_frames][>= ceil(n_bits/8)] (or [max_frames][...]: one row) decode returns: bit t < n_bits of every frame, bit t being
+        bit 7 - t%8 of byte t/8, is XORed with the sequence of x^9 + x^5 + 1 from its start (dab.dab_prbs); the bits at or behind n_bits
+        in the last byte are copied unchanged.  n_frames: int32 CUDA [rows], frames at or behind it are neither read nor written, or
+        None: all.  returns uint8 [rows][max_frames][ceil(n_bits/8)]; out reuses a tensor (its last stride is the frame stride);
+        in_place=True writes into `frames`.  Dispersal is its own inverse.  Nothing is copied to the host."""
+        t = self.torch
+        n_bits = int(n_bits)
+        if n_bits < 0:
+            raise ValueError("n_bits must not be negative")
+        nb = (n_bits + 7) // 8
+        rows, mf, stride = _args.packets(frames, "frames", nb)
+        if in_place:
+            if out is not None:
+                raise ValueError("in_place=True writes into frames: no out")
+            d_out, ostride = frames, stride
+        else:
+            d_out = self._empty(tuple(frames.shape[:-1]) + (nb,), t.uint8) if out is None else out
+            orows, omf, ostride = _args.packets(d_out, "out", nb)
+            if (orows, omf) != (rows, mf):
+                raise ValueError(f"out must hold [{rows}][{mf}] frames")
+        _args.counts(n_frames, rows, "n_frames")
+        if rows * mf == 0 or nb == 0:
+            return d_out
+        _lib.check(_lib.load().vit_hip_dab_descramble_batch(self._handle._h, _ptr(frames), stride, rows, mf, _ptr(n_frames), n_bits,
+                                                            _ptr(d_out), ostride, self._stream()))
+        return d_out
