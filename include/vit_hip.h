@@ -208,7 +208,16 @@ int vit_hip_export_decisions(vit_hip_handle h, const void* d_workspace, size_t f
  *   d_source_index  [symbols_per_frame] int32: index into the frame's punctured symbols, or < 0 for a punctured position,
  *                   which reads as the erasure value 0 (examples/run_punctured_decoder.cpp:165).  The same map serves every
  *                   frame; for a puncturing mask it is the exclusive prefix sum of the mask where the mask is set.
- *   d_symbols_out   [frames][symbols_per_frame] soft_t */
+ *   d_symbols_out   [frames][symbols_per_frame] soft_t
+ * The rule: with j = d_source_index[k], out[f][k] = punctured[f][j] where 0 <= j and (size_t)j < punctured_per_frame, else 0.  An entry
+ * at or above punctured_per_frame is out of range and reads as the erasure too (the rule vit_hip_sync_build / vit_hip_sync_search and
+ * vit_hip_dab_deinterleave_batch keep for the same map); the map need not be monotonic.  The host cannot see the map, the kernel bounds
+ * it: whatever the map holds, nothing outside the buffers is read or written.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the output untouched, for a NULL handle, a NULL d_punctured, d_source_index
+ * or d_symbols_out, symbols_per_frame not a multiple of R, more than (2^31 - 1) * 256 groups of 8 output symbols (too large for one
+ * launch), d_punctured or d_symbols_out not aligned to soft_t, d_source_index not aligned to 4 bytes, d_symbols_out overlapping
+ * d_punctured[0 .. frames * punctured_per_frame) or the map.  frames = 0 or symbols_per_frame = 0 returns VIT_HIP_OK with no work
+ * (whatever the buffer pointers are).  One kernel on `stream`, nothing allocated or synchronised: the call can be captured into a hipGraph. */
 int vit_hip_depuncture_batch(vit_hip_handle h, const void* d_punctured, size_t punctured_per_frame,
                              const int32_t* d_source_index, size_t symbols_per_frame, size_t frames, void* d_symbols_out,
                              vit_hip_stream_t stream);
@@ -484,7 +493,13 @@ int vit_hip_broadcast_table(void* nccl_comm, int root, int rank, int K, int R, i
  * (sigma^2 = 10^(-(ebn0_db - 10 log10 R + 3)/10), scale (high-low)/2 / sqrt(1 + sigma^2): run_snr_ber.cpp:319-359).
  * Every value is a pure function of (seed, first_frame + f, position) through Philox4x32-10: splitting a batch over calls
  * or ranks does not change it.  noise_free != 0: symbols are exactly high / low (ebn0_db ignored).
- *   d_tx_bytes [frames][L/8] or NULL (L % 8 == 0) ; d_symbols [frames][L+K-1][R] soft_t */
+ *   d_tx_bytes [frames][L/8] or NULL (L % 8 == 0) ; d_symbols [frames][L+K-1][R] soft_t
+ * high / low are the two values of the handle's branch table.  A table that shows only one of them (K = 2 always: its single
+ * half-state reads low) takes high = low + soft_decision_max_error / R from the decoder config, for this call, the encoder and
+ * the symbol counts alike (vit_hip_get_info reports it).  L = 0 gives the K - 1 tail steps alone.
+ * Errors: VIT_HIP_ERR_INVALID_ARG for a NULL handle or d_symbols, L % 8 != 0, int16 symbols at an odd address, a batch too large
+ * for one launch; VIT_HIP_ERR_UNSUPPORTED for a handle whose table is not a convolutional code's; nothing is written then.
+ * frames = 0 returns VIT_HIP_OK with no work. */
 int vit_hip_synth_batch(vit_hip_handle h, size_t frames, size_t L, uint64_t seed, uint64_t first_frame, float ebn0_db,
                         int noise_free, uint8_t* d_tx_bytes, void* d_symbols, vit_hip_stream_t stream);
 

@@ -7,42 +7,12 @@
 #include "vit_internal.hpp"
 #include "kernels_lds.hpp"
 #include "kernels_lds2.hpp"
+#include "kernels_depuncture.hpp"
 #include "reg_jit.hpp"
 
 using namespace vit;
 
 namespace vit {
-// depuncturing gather (examples/helpers/puncture_code_helpers.h:17-55 for a batch): out[f][k] = in[f][idx[k]] or 0.  One
-// thread makes 8 consecutive output symbols of one frame (16-byte / 8-byte store); the index map is read once per 8 symbols
-// as two 16-byte loads and stays in L2; source reads are consecutive because the map is monotonic.
-template <typename T>
-__global__ void depuncture_kernel(const T* __restrict__ in, size_t in_stride, const int32_t* __restrict__ idx, size_t n_out,
-                                  size_t frames, T* __restrict__ out) {
-    const size_t chunks = (n_out + 7) / 8;
-    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= chunks * frames) return;
-    const size_t f = gid / chunks, k0 = (gid % chunks) * 8;
-    const T* src = in + f * in_stride;
-    T* dst = out + f * n_out + k0;
-    T v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const size_t k = k0 + i;
-        const int32_t j = k < n_out ? idx[k] : -1;
-        v[i] = j >= 0 ? src[j] : (T)0;
-    }
-    if (k0 + 8 <= n_out && ((uintptr_t)dst % (8 * sizeof(T))) == 0) {
-        typedef T vec8 __attribute__((ext_vector_type(8)));
-        vec8 w;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = v[i];
-        *(vec8*)dst = w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (k0 + i < n_out) dst[i] = v[i];
-    }
-}
 // ViterbiDecoder_Core::reset (core.h:202-211) for a batch: metrics [F][N] error_t
 template <typename error_t>
 __global__ void reset_kernel(error_t* met, const uint32_t* start, size_t frames, uint32_t N, uint32_t init_start, uint32_t init_non_start) {
@@ -57,6 +27,11 @@ __global__ void reset_kernel(error_t* met, const uint32_t* start, size_t frames,
 }  // namespace vit
 
 namespace {
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;                 // differences, not sums: an extent may reach the end of memory
+    return a_bytes && b_bytes && (x >= y ? x - y < b_bytes : y - x < a_bytes);
+}
+
 int lds_waves(int N) {
     if (N <= 256) return 1;
     int w = N / 256;
@@ -239,6 +214,12 @@ static int vit_hip_create_impl(int K, int R, int soft_bytes, int error_bytes, co
 
     for (int k = 0; k < 4; ++k)
         h->cfg_raw[k] = error_bytes == 1 ? (uint32_t)((const uint8_t*)config)[k] : (uint32_t)((const uint16_t*)config)[k];
+    // a table that never shows a second value (K = 2 always: one half-state per polynomial, and that one reads low) cannot say what
+    // `high` is, and the encoder, the frame generator and the symbol counts would take it for `low`: soft_decision_max_error =
+    // (high - low) R says it.  Only h->high, which those read; the decode kernels keep the values the table gave them (cfg.high below)
+    if (!have_high && h->cfg_raw[0] > 0 && h->cfg_raw[0] % (uint32_t)R == 0 &&
+        low + (int)(h->cfg_raw[0] / (uint32_t)R) <= (soft_bytes == 2 ? 32767 : 127))
+        h->high = low + (int)(h->cfg_raw[0] / (uint32_t)R);
     h->cfg.max_error = (uint16_t)(h->cfg_raw[0] << h->shift);
     h->cfg.init_start = (uint16_t)(h->cfg_raw[1] << h->shift);
     h->cfg.init_non_start = (uint16_t)(h->cfg_raw[2] << h->shift);
@@ -544,7 +525,17 @@ int vit_hip_depuncture_batch(vit_hip_handle h, const void* d_punctured, size_t p
     if (symbols_per_frame % (size_t)h->R != 0)
         return fail(VIT_HIP_ERR_INVALID_ARG, "symbols_per_frame must be a multiple of the code rate R");
     const size_t chunks = (symbols_per_frame + 7) / 8;
-    if (chunks * frames > 0x7FFFFFFFull * 256ull) return fail(VIT_HIP_ERR_INVALID_ARG, "batch too large for one launch");
+    if (frames > 0x7FFFFFFFull * 256ull / chunks) return fail(VIT_HIP_ERR_INVALID_ARG, "batch too large for one launch");
+    const size_t sb = (size_t)h->soft_bytes;
+    if ((uintptr_t)d_punctured % sb || (uintptr_t)d_symbols_out % sb)
+        return fail(VIT_HIP_ERR_INVALID_ARG, "d_punctured and d_symbols_out must be aligned to the symbol type");
+    if ((uintptr_t)d_source_index % sizeof(int32_t)) return fail(VIT_HIP_ERR_INVALID_ARG, "d_source_index must be aligned to 4 bytes");
+    // the extents the kernel can touch (the map is bounded by punctured_per_frame on the device); an input too large to state is "all of memory"
+    const size_t out_b = frames * symbols_per_frame * sb;
+    const size_t in_b = punctured_per_frame > (size_t)-1 / sb / frames ? (size_t)-1 - (uintptr_t)d_punctured : frames * punctured_per_frame * sb;
+    if (ranges_overlap(d_symbols_out, out_b, d_punctured, in_b)) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols_out overlaps d_punctured");
+    if (ranges_overlap(d_symbols_out, out_b, d_source_index, symbols_per_frame * sizeof(int32_t)))
+        return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols_out overlaps d_source_index");
     VIT_HIP_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((chunks * frames + 255) / 256);

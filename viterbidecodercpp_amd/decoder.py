@@ -575,7 +575,12 @@ class BatchDecoder(_OuterChain):
     def depuncture(self, punctured, mask, out=None):
         """Depuncturing front-end (examples/helpers/puncture_code_helpers.h:17-55) for a batch: `punctured` is the device
         tensor [F][P] of transmitted symbols, `mask` the puncturing vector over one whole frame (truthy = transmitted, one
-        entry per mother-code symbol, S*R in all); returns [F][S][R] with 0 (erasure) at the punctured positions."""
+        entry per mother-code symbol, S*R in all); returns [F][S][R] with 0 (erasure) at the punctured positions.
+        The map handed to vit_hip_depuncture_batch is the mask's exclusive prefix sum where the mask is set, -1 elsewhere.  The
+        call's own rule is wider: entry j selects punctured[f][j] only where 0 <= j < P, every other entry -- negative, or at or
+        above P -- reads as the erasure 0; whatever the map holds, nothing outside the buffers is read or written.  The call
+        rejects (ValueError, nothing launched) buffers not aligned to the symbol type, a map not aligned to 4 bytes and an
+        `out` that overlaps `punctured` or the map."""
         t = self.torch
         mask = np.asarray(mask).astype(bool).reshape(-1)
         if mask.size % self.R != 0:

@@ -172,7 +172,7 @@ def philox_info_bytes(frames: int, n_bytes: int, seed: int, first_frame: int = 0
     blk = np.arange((n_bytes + 15) // 16, dtype=np.uint64)[None, :]
     x = philox4x32_10(blk, f & np.uint64(0xFFFFFFFF), 0, f >> np.uint64(32), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
     words = np.stack(x, axis=-1)                                 # [F][blocks][4] little-endian words
-    return np.ascontiguousarray(words).view(np.uint8).reshape(frames, -1)[:, :n_bytes].copy()
+    return np.ascontiguousarray(words).view(np.uint8).reshape(frames, 16 * blk.size)[:, :n_bytes].copy()    # (n_bytes = 0: [F][0])
 
 
 def philox_normals(frames: int, n: int, seed: int, first_frame: int = 0) -> np.ndarray:
