@@ -928,7 +928,7 @@ int vit_hip_lte_rate_dematch_batch(vit_hip_handle h, const void* d_received, siz
  * Batch calls like the others: each only enqueues ONE kernel on `stream` (no memset), allocates nothing, needs no object, workspace or pad
  * buffer, synchronises nothing and can be captured into a hipGraph around vit_hip_decode_batch.
  * Out of scope: the unequal-error-protection profile table (a UEP row is whatever map the caller passes); a fast path for one short
- * push; the Reed-Solomon code and superframe synchronisation of DAB+; OFDM demodulation and frequency de-interleaving. */
+ * push; OFDM demodulation and frequency de-interleaving.  (DAB+ superframes: vit_hip_dabplus_sync / vit_hip_dabplus_au_batch below.) */
 int vit_hip_dab_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in_row_stride, size_t in_frame_stride, size_t rows,
                                    size_t max_frames, const uint32_t* d_n_frames, size_t n_received, const int32_t* d_source_index,
                                    size_t symbols_per_frame, const void* d_hist_in, const uint32_t* d_fill_in, size_t hist_row_stride,
@@ -936,6 +936,64 @@ int vit_hip_dab_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in
 int vit_hip_dab_descramble_batch(vit_hip_handle h, const uint8_t* d_in, size_t frame_stride_bytes, size_t rows, size_t max_frames,
                                  const uint32_t* d_n_frames, size_t n_bits, uint8_t* d_out, size_t out_stride_bytes,
                                  vit_hip_stream_t stream);
+
+/* ---- DAB+ audio superframes (ETSI TS 102 563): Fire-code sync in front of frames_extract, the access-unit table behind rs_decode ------
+ * The logical frames the DAB chain returns carry, in a DAB+ sub-channel of index s = 1 .. 24 (B = 24 s bytes a frame), audio superframes
+ * of five frames: 120 s bytes, the first 110 s of them data, the rest the parity of s RS(120,110) codewords read out by columns (symbol i
+ * of codeword c is byte i s + c: vit_hip_rs_decode_batch with the code (0x11D, fcr 0, prim 1, nroots 10, pad 135) at interleave s).
+ * Which frame starts a superframe is marked by nothing but a checksum: bytes 0 .. 1 are the Fire code of bytes 2 .. 10.  Bit t of
+ * anything is bit 7 - t%8 of byte t/8.
+ * Fire code: the 16-bit CRC with generator x^16 + x^14 + x^13 + x^12 + x^11 + x^5 + x^3 + x^2 + x + 1 (0x782F), register 0 at the start,
+ * nothing reflected, no final XOR (vit_hip_crc_params {16, 0x782F, 0, 0}), over bytes 2 .. 10.
+ *   hit(frame) = crc == byte0 * 256 + byte1, and bytes 0 .. 10 are not all zero (an all-zero header checks trivially).
+ *
+ * vit_hip_dabplus_sync: bit-exact and independent of the algorithm.
+ *   - input: frame (r, f) at d_frames + r * row_stride + f * frame_stride, in bytes (frame_stride = 0 => frame_bytes, row_stride = 0 =>
+ *     max_frames * frame stride; non-zero strides are at least those), frame_bytes >= 11.  Only bytes 0 .. 10 of a frame are read; any base
+ *     alignment.  nf = min(d_n_frames[r], max_frames); d_n_frames == NULL: all max_frames frames;
+ *   - frame0 < 5: frame f is of phase (frame0 + f) mod 5 (a receiver passes the logical frames it has seen so far, mod 5);
+ *   - d_hits [rows][5] and d_count [rows][5] uint32, both required: per phase the frames that hit and the frames looked at.  flags = 0
+ *     overwrites them (no memset by the caller), VIT_HIP_MARKER_ACCUMULATE adds to them, as in vit_hip_marker_search;
+ *   - d_lock [rows] (may be NULL) is computed from the totals as they stand after the call: candidate p has compared = count[p] and errors =
+ *     count[p] - hits[p]; a beats b iff compared_a > 0 and (compared_b == 0 or errors_a * compared_b < errors_b * compared_a), the lower
+ *     phase on a tie.  Written: phase = p * 8 * frame_bytes (the bit phase vit_hip_frames_extract reads at period_bits = 40 * frame_bytes
+ *     with phase0 = frame0 * 8 * frame_bytes), inverted = 0, errors, compared.  With no hit anywhere phase 0 wins with errors == compared:
+ *     that is how a caller sees "not locked".
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_frames, d_hits or d_count, unknown
+ * flag bits, frame_bytes below 11 or 40 * frame_bytes at or above 2^31, frame0 >= 5, a stride that is too small, a count array, total or
+ * lock not aligned to 4 bytes, outputs that overlap each other, the frames or d_n_frames, more than 2^31 - 1 rows or frames per row.
+ * rows = 0 returns VIT_HIP_OK with no work.  It enqueues kernels only (zero, search, pick) on `stream`, allocates nothing, synchronises
+ * nothing and can be captured into a hipGraph in front of vit_hip_frames_extract.
+ *
+ * vit_hip_dabplus_au_batch: bit-exact and independent of the algorithm.
+ *   - input: superframe (r, f) at d_in + (r * max_frames + f) * frame_stride_bytes (0 => 120 s; otherwise >= 110 s), the layout
+ *     vit_hip_frames_extract and vit_hip_rs_decode_batch share.  Only the first 110 s bytes are read.  d_n_frames as above;
+ *   - d_rs_status: int32 [rows * max_frames * s] as vit_hip_rs_decode_batch writes it at interleave s, or NULL;
+ *   - header: bit 6 of byte 2 is dac_rate, bit 5 sbr_flag.  (dac, sbr) = (0,1): n_aus 2, au_start[0] 5; (1,1): 3 and 6; (0,0): 4 and 8;
+ *     (1,0): 6 and 11.  au_start[k], 1 <= k < n_aus, are the 12 bits at bit offset 24 + 12 (k-1); au_start[n_aus] = 110 s.  The header is
+ *     consistent iff au_start[k+1] >= au_start[k] + 3 for every k < n_aus (one data byte and the CRC); the superframe is valid iff it is a
+ *     Fire-code hit and consistent;
+ *   - d_info [rows * max_frames] = fire_ok | consistent << 1 | rs_failed << 2 | (valid ? n_aus : 0) << 4 | byte2 << 8; rs_failed is set
+ *     where any of the superframe's s statuses is negative, 0 with d_rs_status == NULL;
+ *   - d_au [rows * max_frames][6]: every superframe f < nf gets all six entries written.  In a valid one, for k < n_aus: start =
+ *     au_start[k], bytes = au_start[k+1] - au_start[k] - 2, syndrome = the CRC (16, 0x1021, 0xFFFF, 0xFFFF) of those bytes XORed with the
+ *     two bytes behind them: 0 where the access unit checks.  Every other entry is {0, 0, 0xFFFFFFFF}.  Superframes at or behind the count
+ *     are not read, and neither their entries nor their info word are written.
+ * Whatever the header, count and status memory holds, nothing outside the 110 s bytes of a superframe it owns is read.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_in, d_info or d_au, s outside
+ * 1 .. 24, a non-zero stride below 110 s, an array not aligned to 4 bytes, outputs that overlap each other, the superframes, d_rs_status or
+ * d_n_frames, more than 2^31 - 1 rows, frames per row or blocks (256 threads; a superframe takes 384).  rows = 0 or max_frames = 0 returns
+ * VIT_HIP_OK with no work.  ONE kernel on `stream` (no memset), no workspace, nothing allocated or synchronised: it can be captured into a
+ * hipGraph behind vit_hip_rs_decode_batch.
+ * Out of scope: AAC decoding, PAD / X-PAD extraction, compacting the access units into a buffer of their own, DMB and enhanced packet
+ * mode, a lock with decay or a flywheel policy, s > 24, UEP. */
+typedef struct vit_hip_dabplus_au { uint32_t start, bytes, syndrome; } vit_hip_dabplus_au;
+int vit_hip_dabplus_sync(vit_hip_handle h, const uint8_t* d_frames, size_t row_stride, size_t frame_stride, size_t frame_bytes, size_t rows,
+                         size_t max_frames, const uint32_t* d_n_frames, unsigned frame0, unsigned flags, uint32_t* d_hits,
+                         uint32_t* d_count, vit_hip_marker_lock* d_lock, vit_hip_stream_t stream);
+int vit_hip_dabplus_au_batch(vit_hip_handle h, const uint8_t* d_in, size_t frame_stride_bytes, size_t rows, size_t max_frames,
+                             const uint32_t* d_n_frames, unsigned s, const int32_t* d_rs_status, uint32_t* d_info,
+                             vit_hip_dabplus_au* d_au, vit_hip_stream_t stream);
 
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant

@@ -282,6 +282,25 @@ public:
                                            stream),
               "vit_hip_dab_descramble_batch");
     }
+    // DAB+ audio superframes (vit_hip_dabplus_sync / vit_hip_dabplus_au_batch; ETSI TS 102 563).  dabplus_sync counts, per phase
+    // (frame0 + f) mod 5, the logical frames of frame_bytes = 24 s bytes whose first two bytes are the Fire code of the nine behind them,
+    // into d_hits / d_count [rows][5] (flags as marker_search), and writes the lock frames_extract reads at period_bits = 40 * frame_bytes
+    // into d_lock [rows] (may be nullptr).  dabplus_au_table reads the header of every superframe of 120 s bytes (rs_decode at interleave
+    // s in front of it; d_rs_status may be nullptr) and writes d_info [rows * max_frames] and the six {start, bytes, syndrome} entries of
+    // d_au: syndrome 0 where the access unit's CRC-16 checks.
+    void dabplus_sync(const uint8_t* d_frames, size_t rows, size_t max_frames, const uint32_t* d_n_frames, size_t frame_bytes,
+                      unsigned frame0, uint32_t* d_hits, uint32_t* d_count, vit_hip_marker_lock* d_lock = nullptr, unsigned flags = 0,
+                      size_t row_stride = 0, size_t frame_stride = 0, void* stream = nullptr) {
+        check(vit_hip_dabplus_sync(m_hip, d_frames, row_stride, frame_stride, frame_bytes, rows, max_frames, d_n_frames, frame0, flags,
+                                   d_hits, d_count, d_lock, stream),
+              "vit_hip_dabplus_sync");
+    }
+    void dabplus_au_table(const uint8_t* d_in, size_t rows, size_t max_frames, const uint32_t* d_n_frames, unsigned s,
+                          const int32_t* d_rs_status, uint32_t* d_info, vit_hip_dabplus_au* d_au, size_t frame_stride_bytes = 0,
+                          void* stream = nullptr) {
+        check(vit_hip_dabplus_au_batch(m_hip, d_in, frame_stride_bytes, rows, max_frames, d_n_frames, s, d_rs_status, d_info, d_au, stream),
+              "vit_hip_dabplus_au_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -134,3 +134,14 @@ def soft_frames(x, dtype, what, least):
     if (mf > 1 and fs < least) or (rows > 1 and rs < mf * (fs or least)):
         raise ValueError(f"the frames of {what} overlap")
     return rows, mf, rs, fs
+
+
+def dabplus_frames(x, frame_bytes, frame0):
+    """(rows, max_frames, row stride, frame stride), in bytes, of the logical frames of a dabplus_sync call: the rule of soft_frames on
+    uint8, frame_bytes at least 11 and small enough for the lock's bit phase, frame0 one of the five places of a superframe"""
+    import torch
+    if not 11 <= frame_bytes <= 0x7FFFFFFF // 40:
+        raise ValueError("frame_bytes must be 11 .. (2^31 - 1) / 40")
+    if not 0 <= frame0 < 5:
+        raise ValueError("frame0 must be 0 .. 4")
+    return soft_frames(x, torch.uint8, "frames", frame_bytes)

@@ -188,6 +188,8 @@ __device__ inline void crc_finish(const CrcArgs& a, const CrcLane& L, uint32_t r
     }
 }
 
+// kernels_dabplus.hpp reuses the device functions above; a kernel is emitted by the one unit that launches it
+#ifndef VIT_CRC_DEVICE_FUNCTIONS_ONLY
 __global__ void __launch_bounds__(CRC_BLOCK) crc_batch_kernel(CrcArgs a) {
     __shared__ uint32_t tab[1024];
     crc_build_tables(tab, a.poly, threadIdx.x, blockDim.x);
@@ -224,5 +226,6 @@ inline int crc_launch_batch(const CrcArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(crc_batch_kernel, dim3((unsigned)crc_blocks(a)), dim3(CRC_BLOCK), 0, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#endif  // VIT_CRC_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace vit

@@ -3,8 +3,8 @@
 // writes the [frames][S][4] symbols the decode reads) and vit_hip_dab_descramble_batch (the energy-dispersal sequence of clause 10 XORed
 // off the decoded bytes).  Both work on the caller's elements alone and read the handle for its device and its symbol width.  The
 // kernels of kernels_dab.hpp are launched only here.  Host-side logic only: argument checking and the launches.
-// Out of scope: the UEP profile table; a fast path for one short push; DAB+ Reed-Solomon and superframe sync; OFDM demodulation and
-// frequency de-interleaving.
+// Out of scope: the UEP profile table; a fast path for one short push; OFDM demodulation and frequency de-interleaving.  DAB+
+// superframes are vit_dabplus.hip.
 #include "vit_internal.hpp"
 #include "kernels_dab.hpp"
 

@@ -24,6 +24,8 @@
 //                    decode reads (kernels_lte.hpp)
 //   vit_dab.hip      the DAB receive chain around the decode: time de-interleaver fused with depuncturing in front, energy-dispersal
 //                    removal behind (kernels_dab.hpp)
+//   vit_dabplus.hip  DAB+ audio superframes behind it: Fire-code superframe sync, the access-unit table and its CRCs
+//                    (kernels_dabplus.hpp, which takes the device functions of kernels_crc.hpp without its kernel)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 """The outer chain of a receiver on the GPU, behind the Viterbi decoder: frame marker search, frame extraction, Reed-Solomon decoding,
-the convolutional de-interleaver, DVB-S energy-dispersal removal, the frame check (CRC) and DAB energy-dispersal removal -- the routes of the C ABI that work on the
-caller's bytes alone and read the handle only for its device (csrc/vit_marker.hip, vit_frames.hip, vit_rs.hip, vit_dvb.hip, vit_crc.hip,
-vit_dab.hip)."""
+the convolutional de-interleaver, DVB-S energy-dispersal removal, the frame check (CRC), DAB energy-dispersal removal and the DAB+
+superframe sync and access-unit table -- the routes of the C ABI that work on the caller's bytes alone and read the handle only for its
+device (csrc/vit_marker.hip, vit_frames.hip, vit_rs.hip, vit_dvb.hip, vit_crc.hip, vit_dab.hip, vit_dabplus.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -284,3 +284,57 @@ class _OuterChain:
         _lib.check(_lib.load().vit_hip_dab_descramble_batch(self._handle._h, _ptr(frames), stride, rows, mf, _ptr(n_frames), n_bits,
                                                             _ptr(d_out), ostride, self._stream()))
         return d_out
+
+    def dabplus_sync(self, frames, frame_bytes: int = None, n_frames=None, frame0: int = 0, out=None, accumulate=False):
+        """DAB+ superframe synchronisation (vit_hip_dabplus_sync; ETSI TS 102 563) on `frames`, the uint8 CUDA tensor
+        [rows][max_frames][>= frame_bytes] of logical frames DabSubchannelDecoder.push returns (or [max_frames][...]: one row; any view
+        whose frames are contiguous and evenly spaced; frame_bytes = 24 s defaults to the last dimension and is at least 11): frame f
+        hits where its bytes 0 .. 1 are the Fire code (dabplus.FIRECODE) of bytes 2 .. 10 and the eleven are not all zero, and counts
+        for phase (frame0 + f) mod 5.  n_frames: int32 CUDA [rows] or None: all.  returns (hits, count, lock): int32 CUDA [rows][5],
+        [rows][5] and [rows][4] = (phase, inverted, errors, compared), the phase in bits as frames_extract reads it at period = 40 *
+        frame_bytes with phase0 = frame0 * 8 * frame_bytes; errors == compared means no frame has hit.  out = (hits, count, lock) reuses
+        those tensors; with accumulate=True the call adds to the totals they hold and the lock is that of the totals.  Nothing is copied
+        to the host."""
+        t = self.torch
+        fb = int(frames.shape[-1]) if frame_bytes is None else int(frame_bytes)
+        rows, mf, rs, fs = _args.dabplus_frames(frames, fb, int(frame0))
+        _args.counts(n_frames, rows, "n_frames")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True adds to the totals of out=(hits, count, lock)")
+            out = (self._empty((rows, 5), t.int32), self._empty((rows, 5), t.int32), self._empty((rows, 4), t.int32))
+        hits, count, lock = out
+        for x, n, what in ((hits, 5, "out[0]"), (count, 5, "out[1]"), (lock, 4, "out[2]")):
+            _args.dense(x, t.int32, rows * n, what)
+        _lib.check(_lib.load().vit_hip_dabplus_sync(self._handle._h, _ptr(frames), rs, fs, fb, rows, mf, _ptr(n_frames), int(frame0),
+                                                    _lib.MARKER_ACCUMULATE if accumulate else 0, _ptr(hits), _ptr(count), _ptr(lock),
+                                                    self._stream()))
+        return hits, count, lock
+
+    def dabplus_au_table(self, superframes, s: int, n_frames=None, rs_status=None, out=None):
+        """the access-unit table of DAB+ audio superframes (vit_hip_dabplus_au_batch) on `superframes`, the uint8 CUDA tensor
+        [rows][max_frames][>= 110 s] frames_extract wrote at period 960 s and rs_decode(dabplus.DABPLUS_RS_120_110, interleave=s)
+        corrected (or [max_frames][...]: one row; the last stride is the frame stride).  n_frames: int32 CUDA [rows], superframes at
+        or behind it are neither read nor written and neither are their entries, or None: all.  rs_status: the int32
+        [rows][max_frames][s] rs_decode returned, or None.  returns (info, au): int32 CUDA [rows][max_frames] = fire_ok | consistent <<
+        1 | rs_failed << 2 | n_aus << 4 | byte2 << 8 (n_aus 0 unless the superframe is valid) and int32 [rows][max_frames][6][3] =
+        (start, bytes, syndrome) per access unit: syndrome 0 where its CRC-16 checks, (0, 0, -1) for a slot without one.  Both hold the
+        uint32 values of the ABI.  out = (info, au) reuses those tensors.  Nothing is copied to the host."""
+        t = self.torch
+        s = int(s)
+        if not 1 <= s <= 24:
+            raise ValueError("s must be 1 .. 24")
+        rows, mf, stride = _args.packets(superframes, "superframes", 110 * s)
+        _args.counts(n_frames, rows, "n_frames")
+        if rs_status is not None:
+            _args.dense(rs_status, t.int32, rows * mf * s, "rs_status")
+        shape = tuple(superframes.shape[:-1])
+        if out is None:
+            out = (self._empty(shape, t.int32), self._empty(shape + (6, 3), t.int32))
+        info, au = out
+        _args.dense(info, t.int32, rows * mf, "out[0]"), _args.dense(au, t.int32, rows * mf * 18, "out[1]")
+        if rows * mf == 0:
+            return info, au
+        _lib.check(_lib.load().vit_hip_dabplus_au_batch(self._handle._h, _ptr(superframes), stride, rows, mf, _ptr(n_frames), s,
+                                                        _ptr(rs_status), _ptr(info), _ptr(au), self._stream()))
+        return info, au
