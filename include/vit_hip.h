@@ -995,6 +995,80 @@ int vit_hip_dabplus_au_batch(vit_hip_handle h, const uint8_t* d_in, size_t frame
                              const uint32_t* d_n_frames, unsigned s, const int32_t* d_rs_status, uint32_t* d_info,
                              vit_hip_dabplus_au* d_au, vit_hip_stream_t stream);
 
+/* ---- the IEEE 802.11a/g OFDM data path: de-interleave, SIGNAL parse, descramble, FCS ------------------------------------------------
+ * The OFDM PHY of 802.11a/g (clause 17; 802.11p / j at half and quarter clock) sends the K = 7, R = 1/2 code (g0 = 133, g1 = 171 octal),
+ * punctured to 2/3 and 3/4, through a per-OFDM-symbol bit interleaver, behind a 7-bit self-synchronising scrambler, with a CRC-32 FCS.
+ * These three calls stand around vit_hip_decode_batch on a handle of K = 7, R = 2 whose polynomials are, in this ABI's convention (bit
+ * k of a polynomial taps the input bit of k steps ago), (109, 79): A[n] = x[n]^x[n-2]^x[n-3]^x[n-5]^x[n-6], B[n] =
+ * x[n]^x[n-1]^x[n-2]^x[n-3]^x[n-6].  Decoded bit t of a frame is bit 7 - t%8 of byte t/8.
+ * A rate index m = 0 .. 7 stands for 6, 9, 12, 18, 24, 36, 48, 54 Mbit/s: N_BPSC = 1, 1, 2, 2, 4, 4, 6, 6; code rate 1/2, 3/4, 1/2, 3/4,
+ * 1/2, 3/4, 2/3, 3/4; N_CBPS = 48 N_BPSC; N_DBPS = 24, 36, 48, 72, 96, 144, 192, 216; SIGNAL RATE bits R1 R2 R3 R4 = 1101, 1111, 0101,
+ * 0111, 1001, 1011, 0001, 0011; s = max(N_BPSC / 2, 1).
+ * Per-frame uint32 arguments (d_rate, d_n_sym, d_n_steps, d_length) are read at element f * stride of their array, the stride in
+ * uint32 elements (0 => 1): with stride 5 they point into the vit_hip_wifi_signal structs vit_hip_wifi_signal_batch wrote.
+ *
+ * vit_hip_wifi_deinterleave_batch: de-interleaves and depunctures in one gather, bit-exact and independent of the algorithm; soft_t is
+ * the handle's symbol type and values pass through unchanged.  It writes the [frames][S][2] buffer vit_hip_decode_batch reads with
+ * L = S - 6.
+ *   - input: frame f is max_sym * N_CBPS(m_f) soft bits at d_in + f * in_frame_stride (elements; 0 => max_sym * 288; a non-zero stride is
+ *     at least max_sym * N_CBPS of the largest rate d_rate allows: 288 with d_rate), OFDM symbols consecutive, each in transmit order;
+ *   - m_f = d_rate ? d_rate[f] (any value) : rate; n_sym_f = min(d_n_sym ? d_n_sym[f] : max_sym, max_sym); n_steps_f = min(d_n_steps ?
+ *     d_n_steps[f] : n_sym_f * N_DBPS, n_sym_f * N_DBPS, S); a frame with m_f > 7 has n_steps_f = 0;
+ *   - for step n < S and output o (0 = A, 1 = B): n >= n_steps_f gives 0, the erasure of vit_hip_depuncture_batch.  Otherwise q = 2 n + o
+ *     is the index in the mother code stream and c its place in the punctured one: rate 1/2, c = q; rate 2/3, of every four A1 B1 A2 B2 the
+ *     fourth is not sent (output 0), c = 3 (q / 4) + q % 4; rate 3/4, of every six A1 B1 A2 B2 A3 B3 the fourth and fifth are not sent,
+ *     c = 4 (q / 6) + (0, 1, 2, -, -, 3)[q % 6].  With y = c / N_CBPS, k = c % N_CBPS: i = (N_CBPS / 16) (k % 16) + k / 16, j = s (i / s) +
+ *     (i + N_CBPS - 16 i / N_CBPS) % s (integer divisions), out[f][n][o] = in[f][y N_CBPS + j].  N_CBPS = 48: k = 1 gives j = 3; N_CBPS = 192:
+ *     k = 1 gives j = 13; k -> j is a permutation at every rate.
+ * Every one of the 2 S outputs of every frame is always written; whatever the rate and count memory holds, nothing outside d_in[f *
+ * stride .. + max_sym * N_CBPS(m_f)) is read.  The erasures behind n_steps_f are what lets a decode that ends in state 0 at step S be a
+ * decode to the best-connected state at the tail: the encoder is in state 0 only behind the six tail bits at step 16 + 8 LENGTH + 6, and
+ * the pad bits behind them are scrambled.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the output untouched, for a NULL handle, d_in or d_symbols_out, a handle
+ * with R != 2, rate > 7 without d_rate, with frames > 0 max_sym = 0 or S = 0, max_sym * 288 at or above 2^32, S at or above 2^31 - 1, a
+ * stride that is too small, d_in not aligned to soft_t, d_symbols_out or a count array not aligned to 4 bytes, an output that overlaps the
+ * input or a count array, frames * 2 S symbols filling 2^32 dwords or more.  frames = 0 returns VIT_HIP_OK with no work.
+ *
+ * vit_hip_wifi_signal_batch: the SIGNAL field is one BPSK rate-1/2 OFDM symbol: de-interleave it with rate = 0, max_sym = 1, S = 24 and
+ * decode with L = 18, which gives 3 bytes a frame.  The parser reads them at d_bytes + f * frame_stride_bytes (0 => 3) and writes d_signal
+ * [frames]: decoded bits 0 .. 3 are R1 .. R4 (rate_index; 8 for a pattern not in the table), bit 4 is reserved, bits 5 .. 16 LENGTH, LSB
+ * first, bit 17 even parity over bits 0 .. 16.  valid = 1 where the pattern is known, the parity holds, the reserved bit is 0 and length
+ * >= 1.  n_steps = 16 + 8 length + 6 and n_sym = ceil(n_steps / N_DBPS) where valid, else both 0: the next stage erases the frame.
+ * Errors: INVALID_ARG for a NULL handle, d_bytes or d_signal, a non-zero stride below 3, d_signal not aligned to 4 bytes or overlapping
+ * d_bytes, more than 2^31 - 1 blocks.  frames = 0: no work.
+ *
+ * vit_hip_wifi_data_batch: works on the bytes vit_hip_decode_batch wrote for the DATA field, frame f at d_bytes + f * frame_stride_bytes
+ * (0 => ceil((S - 6) / 8)), n_bits = S - 6 decoded bits d[t] a frame.
+ *   - scrambler: p[t] = d[t] for t < 7 (the first seven SERVICE bits are zero: these are the sequence itself), p[t] = p[t-4] ^ p[t-7]
+ *     behind them, period 127; with p[0..6] = 0000111 the sequence goes on 0 1111 0010 ..., in bytes 0E F2.  u[t] = d[t] ^ p[t];
+ *   - len_f = min(d_length[f], max_length), cut further so that 16 + 8 len_f <= n_bits.  PSDU octet g < len_f, bit b (LSB = 0), is
+ *     u[16 + 8 g + b], written to d_psdu + f * psdu_stride + g (psdu_stride 0 => max_length); octets at or behind len_f are not written;
+ *   - d_status[f] = {length_used = len_f; seed = p[0..6] as a number, p[0] highest (0: no scrambler state gives it; the frame is still
+ *     written); service = u[0..15], u[0] lowest (0 from a conforming sender); fcs_syndrome = CRC32(psdu[0 .. len-4)) ^ LE32(psdu[len-4 ..
+ *     len)), CRC32 the ISO-HDLC one (zlib): 0 where the frame checks, 0xFFFFFFFF where len_f < 4}.  In transmit order that is the
+ *     non-reflected code (32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF) of vit_hip_crc_batch over frame bits 16 .. 16 + 8 (len - 4) of u, XORed
+ *     with the 32 bits behind them MSB-first, the whole read backwards: fcs_syndrome is the 32-bit reversal of that syndrome.
+ * Whatever d_length holds, nothing outside the ceil(n_bits / 8) bytes of a frame is read.
+ * Errors: INVALID_ARG for a NULL handle or buffer, S below 22 or at or above 2^31 - 1, max_length at or above 2^28, a stride below
+ * ceil((S - 6) / 8), a non-zero psdu_stride below min(max_length, (S - 22) / 8), d_length or d_status not aligned to 4 bytes, outputs
+ * that overlap each other, d_bytes or d_length, more than 2^31 - 1 blocks (256 threads; a frame takes 1 .. 64 of them by the longest PSDU
+ * the call allows).  frames = 0: no work.
+ * Batch calls like the others: each only enqueues ONE kernel on `stream` (no memset), allocates nothing, needs no workspace, synchronises
+ * nothing and can be captured into a hipGraph around vit_hip_decode_batch.
+ * Out of scope: synchronisation, channel estimation and demapping; 802.11n/ac (other interleavers, LDPC, BCC with several encoders) and
+ * 802.11b; bucketing frames by length; a transmitter on the card; A-MPDU delimiters. */
+typedef struct vit_hip_wifi_signal { uint32_t rate_index, length, n_sym, n_steps, valid; } vit_hip_wifi_signal;
+typedef struct vit_hip_wifi_status { uint32_t length_used, seed, service, fcs_syndrome; } vit_hip_wifi_status;
+int vit_hip_wifi_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in_frame_stride, size_t frames, size_t max_sym,
+                                    unsigned rate, const uint32_t* d_rate, const uint32_t* d_n_sym, const uint32_t* d_n_steps,
+                                    size_t count_stride, size_t S, void* d_symbols_out /* [frames][S][2] soft_t */,
+                                    vit_hip_stream_t stream);
+int vit_hip_wifi_signal_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t frame_stride_bytes, size_t frames,
+                              vit_hip_wifi_signal* d_signal, vit_hip_stream_t stream);
+int vit_hip_wifi_data_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t frame_stride_bytes, size_t frames, size_t S,
+                            const uint32_t* d_length, size_t length_stride, size_t max_length, uint8_t* d_psdu, size_t psdu_stride,
+                            vit_hip_wifi_status* d_status, vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

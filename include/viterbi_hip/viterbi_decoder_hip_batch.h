@@ -301,6 +301,31 @@ public:
         check(vit_hip_dabplus_au_batch(m_hip, d_in, frame_stride_bytes, rows, max_frames, d_n_frames, s, d_rs_status, d_info, d_au, stream),
               "vit_hip_dabplus_au_batch");
     }
+    // The IEEE 802.11a/g OFDM data path around decode (vit_hip_wifi_deinterleave_batch / _signal_batch / _data_batch), a decoder of K = 7,
+    // R = 2 with the polynomials (109, 79).  wifi_deinterleave undoes the per-symbol interleaver and the puncturing of rate index 0 .. 7 in
+    // one gather: frame f's max_sym * N_CBPS soft bits at d_in + f * in_frame_stride (0: max_sym * 288) -> d_symbols_out [frames][S][2], 0
+    // behind the frame's n_steps.  d_rate / d_n_sym / d_n_steps (nullptr: `rate`, max_sym, n_sym * N_DBPS) are read at element f *
+    // count_stride (0: 1): with 5 they point at the rate_index, n_sym and n_steps of the vit_hip_wifi_signal structs wifi_signal_parse
+    // wrote from the 3 decoded bytes of every SIGNAL field.  wifi_descramble recovers the scrambler seed of the decoded DATA bytes,
+    // descrambles, writes PSDU octets (frame f at d_psdu + f * psdu_stride, 0: max_length) and the FCS syndrome at the frame's own length.
+    void wifi_deinterleave(const soft_t* d_in, size_t frames, size_t max_sym, size_t S, soft_t* d_symbols_out, unsigned rate = 0,
+                           const uint32_t* d_rate = nullptr, const uint32_t* d_n_sym = nullptr, const uint32_t* d_n_steps = nullptr,
+                           size_t count_stride = 0, size_t in_frame_stride = 0, void* stream = nullptr) {
+        check(vit_hip_wifi_deinterleave_batch(m_hip, d_in, in_frame_stride, frames, max_sym, rate, d_rate, d_n_sym, d_n_steps, count_stride, S,
+                                              d_symbols_out, stream),
+              "vit_hip_wifi_deinterleave_batch");
+    }
+    void wifi_signal_parse(const uint8_t* d_bytes, size_t frames, vit_hip_wifi_signal* d_signal, size_t frame_stride_bytes = 0,
+                           void* stream = nullptr) {
+        check(vit_hip_wifi_signal_batch(m_hip, d_bytes, frame_stride_bytes, frames, d_signal, stream), "vit_hip_wifi_signal_batch");
+    }
+    void wifi_descramble(const uint8_t* d_bytes, size_t frames, size_t S, const uint32_t* d_length, size_t length_stride, size_t max_length,
+                         uint8_t* d_psdu, vit_hip_wifi_status* d_status, size_t psdu_stride = 0, size_t frame_stride_bytes = 0,
+                         void* stream = nullptr) {
+        check(vit_hip_wifi_data_batch(m_hip, d_bytes, frame_stride_bytes, frames, S, d_length, length_stride, max_length, d_psdu, psdu_stride,
+                                      d_status, stream),
+              "vit_hip_wifi_data_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -145,3 +145,35 @@ def dabplus_frames(x, frame_bytes, frame0):
     if not 0 <= frame0 < 5:
         raise ValueError("frame0 must be 0 .. 4")
     return soft_frames(x, torch.uint8, "frames", frame_bytes)
+
+
+def wifi_rows(x, dtype, least, what):
+    """(frames, row stride in elements) of a tensor of `dtype` [frames][>= least] with contiguous rows, or one frame [>= least]: the soft
+    bits of wifi_deinterleave, the decoded bytes of wifi_signal_parse and wifi_descramble.  Rows lie in ascending order and do not
+    overlap.  The stride of a single row is its width: the ABI takes the bytes a call may read from the stride, and its own default (0)
+    may be wider than the tensor"""
+    if device(x, dtype, what).dim() not in (1, 2) or (x.numel() and x.stride(-1) != 1) or x.shape[-1] < least:
+        raise ValueError(f"{what} must be [frames][>= {least}] of {dtype} with contiguous rows")
+    frames = 1 if x.dim() == 1 else int(x.shape[0])
+    stride = int(x.stride(0)) if frames > 1 else int(x.shape[-1])
+    if frames > 1 and stride < least:
+        raise ValueError(f"the frames of {what} overlap")
+    return frames, stride
+
+
+def wifi_soft(x, dtype, max_sym, S, rate, per_frame):
+    """(frames, row stride) of the soft bits of a wifi_deinterleave call: the rule of wifi_rows with at least max_sym OFDM symbols a row,
+    of N_CBPS(rate) soft bits each, or of 288 where the rate is per frame on the device.  max_sym and S at least 1, rate 0 .. 7"""
+    from .wifi import WIFI_RATES
+    if max_sym < 1 or S < 1 or not 0 <= rate <= 7:
+        raise ValueError("max_sym and S must be at least 1, rate 0 .. 7")
+    return wifi_rows(x, dtype, max_sym * (WIFI_RATES[7].n_cbps if per_frame else WIFI_RATES[rate].n_cbps), "soft")
+
+
+def wifi_signal(x, frames, what="signal"):
+    """the [frames][5] int32 tensor wifi_signal_parse returns -- (rate_index, length, n_sym, n_steps, valid), the uint32 values of the
+    ABI --, dense: the per-frame arguments of the next stages point into it at an element stride of 5"""
+    import torch
+    if dense(x, torch.int32, frames * 5, what).dim() != 2 or x.shape[1] != 5:
+        raise ValueError(f"{what} must be an int32 CUDA tensor [{frames}][5]")
+    return x

@@ -35,6 +35,8 @@ LTE_CRC24A = CRCCode(24, 0x864CFB, 0, 0)
 LTE_CRC24B = CRCCode(24, 0x800063, 0, 0)
 LTE_CRC8 = CRCCode(8, 0x9B, 0, 0)
 MPEG2_CRC32 = CRCCode(32, 0x04C11DB7, 0xFFFFFFFF, 0)  # PSI sections (ISO/IEC 13818-1)
+# the 802.11 FCS over bits in transmit order (octets LSB first): zlib.crc32 of the octets is the 32-bit reversal of this code's value
+WIFI_FCS = CRCCode(32, 0x04C11DB7, 0xFFFFFFFF, 0xFFFFFFFF)
 STOCK_CRC_CODES = {"CCSDS_CRC16": CCSDS_CRC16, "LTE_CRC16": LTE_CRC16, "DAB_CRC16": DAB_CRC16, "LTE_CRC24A": LTE_CRC24A,
                    "LTE_CRC24B": LTE_CRC24B, "LTE_CRC8": LTE_CRC8, "MPEG2_CRC32": MPEG2_CRC32}
 

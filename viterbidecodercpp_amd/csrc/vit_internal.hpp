@@ -26,6 +26,8 @@
 //                    removal behind (kernels_dab.hpp)
 //   vit_dabplus.hip  DAB+ audio superframes behind it: Fire-code superframe sync, the access-unit table and its CRCs
 //                    (kernels_dabplus.hpp, which takes the device functions of kernels_crc.hpp without its kernel)
+//   vit_wifi.hip     the IEEE 802.11a/g OFDM data path: de-interleaver fused with depuncturing in front of the decode, the SIGNAL
+//                    parser, descrambling and the FCS behind it (kernels_wifi.hpp, which takes those device functions likewise)
 #pragma once
 #include <hip/hip_runtime.h>
 

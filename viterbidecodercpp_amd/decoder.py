@@ -627,6 +627,89 @@ class BatchDecoder(_OuterChain):
             _ptr(out), self._stream()))
         return out
 
+    def wifi_deinterleave(self, soft, max_sym: int, S: int, rate: int = 0, rates=None, n_sym=None, n_steps=None, signal=None, out=None):
+        """the 802.11a/g de-interleaver fused with depuncturing, in front of decode (vit_hip_wifi_deinterleave_batch): soft, a CUDA tensor
+        of the decoder's symbol dtype [frames][>= max_sym * N_CBPS] with contiguous rows (frame f's OFDM symbols in transmit order; 288 a
+        symbol where the rate is per frame) -> symbols [frames][S][2], which decode reads with L = S - 6.  rate: one index 0 .. 7 for all
+        frames; or per frame on the device: rates / n_sym / n_steps, int32 CUDA [frames] each (None: `rate`, max_sym, n_sym * N_DBPS), or
+        signal, the [frames][5] tensor wifi_signal_parse returned, whose rate_index, n_sym and n_steps columns are read in place.  Steps
+        at or behind a frame's n_steps, punctured bits and frames of a rate above 7 are 0, the erasure.  The rule on the host:
+        wifi.wifi_deinterleave_numpy.  A decoder of rate 1/2 only.  Nothing is copied to the host."""
+        max_sym, S, rate = int(max_sym), int(S), int(rate)
+        if self.R != 2:
+            raise ValueError("the 802.11a/g data path feeds a rate 1/2 decoder")
+        frames, stride = _args.wifi_soft(soft, self._soft_dtype, max_sym, S, rate, signal is not None or rates is not None)
+        if signal is not None:
+            if rates is not None or n_sym is not None or n_steps is not None:
+                raise ValueError("signal stands for rates, n_sym and n_steps")
+            at = _args.wifi_signal(signal, frames).data_ptr()
+            p_rate, p_sym, p_steps, cs = C.c_void_p(at), C.c_void_p(at + 8), C.c_void_p(at + 12), 5
+        else:
+            for x, what in ((rates, "rates"), (n_sym, "n_sym"), (n_steps, "n_steps")):
+                _args.counts(x, frames, what)
+            p_rate, p_sym, p_steps, cs = _ptr(rates), _ptr(n_sym), _ptr(n_steps), 1
+        if out is None:
+            out = self._empty((frames, S, 2), self._soft_dtype)
+        _args.dense(out, self._soft_dtype, frames * S * 2, "out")
+        if frames == 0:
+            return out
+        _lib.check(_lib.load().vit_hip_wifi_deinterleave_batch(self._handle._h, _ptr(soft), stride, frames, max_sym, rate, p_rate, p_sym,
+                                                               p_steps, cs, S, _ptr(out), self._stream()))
+        return out
+
+    def wifi_signal_parse(self, bytes, out=None):
+        """the 802.11a/g SIGNAL field (vit_hip_wifi_signal_batch): bytes, uint8 CUDA [frames][>= 3] with contiguous rows -- what decode
+        returns with L = 18 for the SIGNAL symbol de-interleaved at rate 0, max_sym 1, S 24 -- -> int32 CUDA [frames][5] = (rate_index,
+        length, n_sym, n_steps, valid), the uint32 values of the ABI: rate_index 8 for an unknown pattern; valid = 1 where the pattern
+        is known, the parity holds, the reserved bit is 0 and length >= 1; n_steps = 16 + 8 length + 6 and n_sym = ceil(n_steps / N_DBPS)
+        where valid, else 0.  The rule on the host: wifi.wifi_signal_parse_numpy.  Nothing is copied to the host."""
+        t = self.torch
+        frames, stride = _args.wifi_rows(bytes, t.uint8, 3, "bytes")
+        if out is None:
+            out = self._empty((frames, 5), t.int32)
+        _args.wifi_signal(out, frames, "out")
+        if frames == 0:
+            return out
+        _lib.check(_lib.load().vit_hip_wifi_signal_batch(self._handle._h, _ptr(bytes), stride, frames, _ptr(out), self._stream()))
+        return out
+
+    def wifi_descramble(self, bytes, S: int, lengths, max_length: int = None, out=None):
+        """descrambling, PSDU octets and the FCS of 802.11a/g DATA fields (vit_hip_wifi_data_batch): bytes, uint8 CUDA [frames][>=
+        ceil((S - 6) / 8)] with contiguous rows, what decode returns with L = S - 6.  lengths: int32 CUDA [frames], or the [frames][5]
+        tensor wifi_signal_parse returned, whose length column is read in place.  A frame's length is cut at max_length (None: what S
+        holds, (S - 22) / 8) and at what S holds.  returns (psdu, status): uint8 [frames][max_length] of which frame f's first
+        length_used octets are written, and int32 [frames][4] = (length_used, seed, service, fcs_syndrome), the uint32 values of the
+        ABI: seed the scrambler's first seven bits (0: not a scrambler's), service 0 from a conforming sender, fcs_syndrome =
+        zlib.crc32(psdu[:-4]) ^ the last four octets read little-endian: 0 where the frame checks, 0xFFFFFFFF below four octets.  out =
+        (psdu, status) reuses those tensors; psdu rows may be wider.  The rule on the host: wifi.wifi_descramble_numpy.  Nothing is
+        copied to the host."""
+        t = self.torch
+        S = int(S)
+        if S < 22:
+            raise ValueError("S must be at least 22: the SERVICE field and the tail")
+        room = (S - 22) // 8
+        max_length = room if max_length is None else int(max_length)
+        if max_length < 0:
+            raise ValueError("max_length must not be negative")
+        frames, stride = _args.wifi_rows(bytes, t.uint8, (S - 6 + 7) // 8, "bytes")
+        if lengths.dim() == 2:
+            at, ls = C.c_void_p(_args.wifi_signal(lengths, frames, "lengths").data_ptr() + 4), 5
+        else:
+            at, ls = _ptr(_args.dense(lengths, t.int32, frames, "lengths")), 1
+        if out is None:
+            out = (self._empty((frames, max_length), t.uint8), self._empty((frames, 4), t.int32))
+        psdu, status = out
+        pframes, pstride = _args.wifi_rows(psdu, t.uint8, min(max_length, room), "out[0]")
+        if pframes != frames or psdu.dim() != 2:
+            raise ValueError(f"out[0] must hold [{frames}] rows")
+        _args.dense(status, t.int32, frames * 4, "out[1]")
+        if frames == 0:
+            return psdu, status
+        at_psdu = _ptr(psdu) if psdu.numel() else C.c_void_p(status.data_ptr())        # no octet is written: any non-NULL address
+        _lib.check(_lib.load().vit_hip_wifi_data_batch(self._handle._h, _ptr(bytes), stride, frames, S, at, ls, max_length, at_psdu,
+                                                       pstride, _ptr(status), self._stream()))
+        return psdu, status
+
     def dab_deinterleave(self, frames, n_frames=None, source_index=None, hist=None, fill=None, n_received: int = None, out=None):
         """the DAB time de-interleaver fused with depuncturing, in front of decode (vit_hip_dab_deinterleave_batch; ETSI EN 300 401
         clauses 12 and 11).  frames: the received soft bits, a CUDA tensor of the decoder's symbol dtype [rows][max_frames][>= n] (or
