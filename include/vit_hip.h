@@ -1069,6 +1069,53 @@ int vit_hip_wifi_data_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t fra
                             const uint32_t* d_length, size_t length_stride, size_t max_length, uint8_t* d_psdu, size_t psdu_stride,
                             vit_hip_wifi_status* d_status, vit_hip_stream_t stream);
 
+/* ---- DVB-T: inner de-interleaver and depuncturing in front of the decode ---------------------------------------------------------------
+ * DVB-T (ETSI EN 300 744) sends the K = 7, R = 1/2 code X = 171, Y = 133 octal punctured to 2/3, 3/4, 5/6 or 7/8 (clause 4.3.3),
+ * demultiplexed into v bit streams that are bit-interleaved in blocks of 126, and symbol-interleaved over the Nmax data carriers of an
+ * OFDM symbol by a permutation H whose direction alternates with the symbol's parity (clause 4.3.4).  Behind the decoder it is the DVB-S
+ * outer chain: sync byte 0x47 every 1632 bits (vit_hip_marker_search, vit_hip_frames_extract), vit_hip_deinterleave_batch at (12, 17),
+ * RS(204,188), vit_hip_dvb_derandomize_batch.  This call is the front, on a handle of K = 7, R = 2 with the stock polynomials (109, 79) =
+ * (133, 171) octal in this ABI's convention: Y is output 0 of a trellis step and X output 1 -- THE SWAP: the standard names X first, the
+ * stock code has it second, and the call writes (Y, X) so that a real broadcast decodes with the stock kernels.
+ *   mode 0, 1, 2 = 2k, 4k, 8k: Mmax = 2048, 4096, 8192; Nmax = 1512, 3024, 6048; Nr = 11, 12, 13.  v = 2, 4, 6 (QPSK, 16-QAM, 64-QAM,
+ *   non-hierarchical).  rate 0 .. 4 = 1/2, 2/3, 3/4, 5/6, 7/8: a period of k = 1, 2, 3, 5, 7 steps sends k + 1 bits, in the order X1 Y1 |
+ *   X1 Y1 Y2 | X1 Y1 Y2 X3 | X1 Y1 Y2 X3 Y4 X5 | X1 Y1 Y2 Y3 Y4 X5 Y6 X7.  steps = Nmax v k / (k + 1) per OFDM symbol (1512 at 2k / QPSK /
+ *   1/2, 31752 at 8k / 64-QAM / 7/8): every symbol holds whole periods and the puncturing phase restarts with it.
+ *   - input: row r at d_in + r * in_row_stride (elements of soft_t, the handle's symbol type; 0 => n_sym * Nmax * v), n_sym OFDM symbols
+ *     of Nmax cells in carrier order, v soft bits a cell, e = 0 the first mapped bit: in[r][y][carrier][e].  Pilots and TPS carriers are
+ *     not in it.  Values pass through unchanged;
+ *   - H: R'_0 = R'_1 = 0, R'_2 = 1, R'_i = (R'_{i-1} >> 1) | (newbit << (Nr - 2)) with newbit the XOR of bits (0, 3) at 2k, (0, 2) at 4k,
+ *     (0, 1, 4, 6) at 8k of R'_{i-1}; R_i has bit Nr-2, Nr-3, .., 0 of R'_i at positions 0 7 5 1 8 2 6 9 3 4 (2k), 7 10 5 8 1 2 4 9 0 3 6
+ *     (4k), 5 11 3 0 10 8 6 9 2 4 1 7 (8k); for i = 0 .. Mmax - 1, h = (i mod 2) 2^(Nr-1) + R_i is the next H(q) where h < Nmax.
+ *     H(0..7) = 0 1024 16 1025 128 1056 2 1280 (2k), 0 2048 64 2176 1024 2080 256 2050 (4k), 0 4096 128 4128 2048 4104 1 5120 (8k);
+ *     sum(q H(q)) mod 65521 = 52702, 9494, 57713;
+ *   - parity of symbol y of row r: (first_r + y) & 1 with first_r = d_parity_in ? d_parity_in[r] : parity.  Interleaver cell q is on
+ *     carrier P(q) = H(q) in an even symbol, H^-1(q) in an odd one.  With d_parity_out, d_parity_out[r] = first_r + n_sym: the counter
+ *     travels between two arrays like the fill of vit_hip_deinterleave_batch, so a captured graph of two calls replays correctly;
+ *   - output: row r at d_symbols_out + r * out_row_stride * 2 elements (out_row_stride in trellis steps; 0 => n_sym * steps), symbol y's
+ *     steps at y * steps: the `pitch` layout of vit_hip_decode_streams, or one row for vit_hip_decode_stream.  For step n of a symbol and
+ *     output o (0 = Y, 1 = X): with j = n mod k, place = (1/2: X 0, Y 1; 2/3: X1 0, Y1 1, Y2 2; 3/4: .., X3 3; 5/6: .., Y4 4, X5 5; 7/8:
+ *     X1 0, Y1 1, Y2 2, Y3 3, Y4 4, X5 5, Y6 6, X7 7); a bit the period does not send gives 0, the erasure of vit_hip_depuncture_batch.
+ *     Otherwise di = (k + 1) (n / k) + place, do = di / v, r = di mod v, e = r / (v / 2) + 2 (r mod (v / 2)), q = 126 (do / 126) +
+ *     (do mod 126 - s_e) mod 126 with s = (0, 63, 105, 42, 21, 84), out[r][y * steps + n][o] = in[r][y][P(q)][e].  At 2k / QPSK / 1/2 in
+ *     an even symbol out[0][1] = in[0][0][0] and out[0][0] = in[0][H(63)][1].
+ * Every one of the 2 n_sym steps outputs of every row is written and nothing between the rows; nothing outside the n_sym * Nmax * v
+ * elements of a row is read.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the output untouched, for a NULL handle, d_in or d_symbols_out, a handle
+ * with R != 2, mode > 2, v not 2, 4 or 6, rate > 4, d_in not aligned to soft_t, d_symbols_out or a parity array not aligned to 4 bytes, at
+ * 8-bit symbols an odd out_row_stride with more than one row (every row starts a dword), a non-zero stride below the row, n_sym * Nmax * v,
+ * rows or a stride at or above 2^32, an input or output of 2^32 dwords or more, rows * n_sym * Nmax / 504 above 2^31 - 8, an output that
+ * overlaps the input or a parity array, d_parity_out overlapping d_parity_in (the same array included) or d_in.  rows = 0 or n_sym = 0
+ * returns VIT_HIP_OK with no work (d_parity_out is not written).
+ * A batch call like the others: it only enqueues ONE kernel on `stream` (no memset), allocates nothing, needs no workspace, synchronises
+ * nothing and can be captured into a hipGraph in front of vit_hip_decode_stream(s).
+ * Out of scope: hierarchical modes, the DVB-H in-depth interleaver, OFDM demodulation, pilots, TPS decoding and demapping, DVB-T2, a
+ * transmitter on the card. */
+int vit_hip_dvbt_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in_row_stride, size_t rows, size_t n_sym, unsigned mode,
+                                    unsigned v, unsigned rate, unsigned parity, const uint32_t* d_parity_in, uint32_t* d_parity_out,
+                                    void* d_symbols_out /* [rows][>= n_sym * steps][2] soft_t */, size_t out_row_stride,
+                                    vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

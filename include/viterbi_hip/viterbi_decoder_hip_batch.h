@@ -326,6 +326,19 @@ public:
                                       d_status, stream),
               "vit_hip_wifi_data_batch");
     }
+    // The front of the DVB-T route (vit_hip_dvbt_deinterleave_batch; ETSI EN 300 744 clauses 4.3.3 and 4.3.4), a decoder of K = 7, R = 2
+    // with the polynomials (109, 79): the inner de-interleaver (symbol, bit, demultiplexer) fused with depuncturing.  Row r's n_sym OFDM
+    // symbols [Nmax][v] at d_in + r * in_row_stride (0: n_sym * Nmax * v) -> n_sym * steps trellis steps (Y, X) at d_symbols_out + r *
+    // out_row_stride * 2 (in steps; 0: n_sym * steps), 0 where the rate sent nothing: what decode_stream(s) reads.  mode 0 .. 2 = 2k, 4k,
+    // 8k; v = 2, 4, 6; rate 0 .. 4 = 1/2, 2/3, 3/4, 5/6, 7/8.  The parity of a row's first symbol is `parity`, or d_parity_in[r]; with
+    // d_parity_out the count goes on there (+ n_sym), ping-ponged between two arrays from call to call.
+    void dvbt_deinterleave(const soft_t* d_in, size_t rows, size_t n_sym, unsigned mode, unsigned v, unsigned rate, soft_t* d_symbols_out,
+                           unsigned parity = 0, const uint32_t* d_parity_in = nullptr, uint32_t* d_parity_out = nullptr,
+                           size_t in_row_stride = 0, size_t out_row_stride = 0, void* stream = nullptr) {
+        check(vit_hip_dvbt_deinterleave_batch(m_hip, d_in, in_row_stride, rows, n_sym, mode, v, rate, parity, d_parity_in, d_parity_out,
+                                              d_symbols_out, out_row_stride, stream),
+              "vit_hip_dvbt_deinterleave_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

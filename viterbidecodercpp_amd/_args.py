@@ -177,3 +177,30 @@ def wifi_signal(x, frames, what="signal"):
     if dense(x, torch.int32, frames * 5, what).dim() != 2 or x.shape[1] != 5:
         raise ValueError(f"{what} must be an int32 CUDA tensor [{frames}][5]")
     return x
+
+
+def dvbt_symbols(x, dtype, cell):
+    """(rows, n_sym, row stride in elements) of the soft bits of a dvbt_deinterleave call: a tensor of `dtype` [rows][n_sym][cell] or
+    [n_sym][cell] (one row), cell = Nmax * v, whose rows are contiguous, lie in ascending order and do not overlap; a view with a larger
+    row stride is read in place.  The stride of a single row is its length"""
+    if device(x, dtype, "symbols").dim() not in (2, 3) or x.shape[-1] != cell:
+        raise ValueError(f"symbols must be [rows][n_sym][{cell}] or [n_sym][{cell}] of {dtype}")
+    rows, n_sym = (1 if x.dim() == 2 else int(x.shape[0])), int(x.shape[-2])
+    if x.numel() and (x.stride(-1) != 1 or (n_sym > 1 and x.stride(-2) != cell)):
+        raise ValueError("the OFDM symbols of a row of symbols must be contiguous")
+    stride = int(x.stride(0)) if x.dim() == 3 and rows > 1 else n_sym * cell
+    if stride < n_sym * cell:
+        raise ValueError("the rows of symbols overlap")
+    return rows, n_sym, stride
+
+
+def dvbt_out(x, dtype, rows, steps):
+    """the row stride in trellis steps of the output of a dvbt_deinterleave call: a tensor of `dtype` [rows][>= steps][2] (or [>= steps][2]
+    with one row) with contiguous rows -- the [n_streams][pitch][R] buffer decode_streams reads, say"""
+    if device(x, dtype, "out").dim() not in (2, 3) or x.shape[-1] != 2 or x.shape[-2] < steps or (1 if x.dim() == 2 else x.shape[0]) != rows:
+        raise ValueError(f"out must be [{rows}][>= {steps}][2] of {dtype}")
+    if x.numel() and (x.stride(-1) != 1 or (x.shape[-2] > 1 and x.stride(-2) != 2) or (x.dim() == 3 and rows > 1 and x.stride(0) % 2)):
+        raise ValueError("the rows of out must be contiguous")
+    if x.dim() == 3 and rows > 1 and x.stride(0) < 2 * steps:
+        raise ValueError("the rows of out overlap")
+    return int(x.stride(0)) // 2 if x.dim() == 3 and rows > 1 else int(x.shape[-2])

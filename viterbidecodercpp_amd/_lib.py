@@ -43,6 +43,7 @@ EXPORTS = [
     "vit_hip_dab_deinterleave_batch", "vit_hip_dab_descramble_batch",
     "vit_hip_dabplus_sync", "vit_hip_dabplus_au_batch",
     "vit_hip_wifi_deinterleave_batch", "vit_hip_wifi_signal_batch", "vit_hip_wifi_data_batch",
+    "vit_hip_dvbt_deinterleave_batch",
 ]
 
 
@@ -185,6 +186,7 @@ def load():
     L.vit_hip_wifi_deinterleave_batch.argtypes = [vp, vp, sz, sz, sz, C.c_uint, vp, vp, vp, sz, sz, vp, vp]
     L.vit_hip_wifi_signal_batch.argtypes = [vp, vp, sz, sz, vp, vp]
     L.vit_hip_wifi_data_batch.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, vp]
+    L.vit_hip_dvbt_deinterleave_batch.argtypes = [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, sz, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

@@ -28,6 +28,8 @@
 //                    (kernels_dabplus.hpp, which takes the device functions of kernels_crc.hpp without its kernel)
 //   vit_wifi.hip     the IEEE 802.11a/g OFDM data path: de-interleaver fused with depuncturing in front of the decode, the SIGNAL
 //                    parser, descrambling and the FCS behind it (kernels_wifi.hpp, which takes those device functions likewise)
+//   vit_dvbt.hip     the front of the DVB-T route: the inner de-interleaver (symbol, bit, demultiplexer) fused with depuncturing in front
+//                    of the stream decode (kernels_dvbt.hpp); behind the decode DVB-T is the DVB-S chain of vit_dvb.hip
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -710,6 +710,42 @@ class BatchDecoder(_OuterChain):
                                                        pstride, _ptr(status), self._stream()))
         return psdu, status
 
+    def dvbt_deinterleave(self, symbols, mode, v: int, rate: int, parity=0, out=None):
+        """the DVB-T inner de-interleaver (symbol, bit, demultiplexer) fused with depuncturing, in front of decode_stream(s)
+        (vit_hip_dvbt_deinterleave_batch; ETSI EN 300 744 clauses 4.3.3, 4.3.4).  symbols: a CUDA tensor of the decoder's symbol dtype
+        [rows][n_sym][Nmax * v] (or [n_sym][Nmax * v]: one row), every OFDM symbol's data cells in carrier order, v soft bits a cell; a
+        view with a larger row stride is read in place.  mode '2k', '4k' or '8k'; v 2, 4 or 6; rate 0 .. 4 = 1/2, 2/3, 3/4, 5/6, 7/8.
+        parity: that of every row's first symbol, an int -- or (counter_in, counter_out), two distinct int32 CUDA tensors [rows]: the
+        first holds every row's parity (any count: its lowest bit), the second receives it plus n_sym, and the next call takes them the
+        other way round.  returns [rows][n_sym * steps][2] ([n_sym * steps][2] for one row given as such), (Y, X) per trellis step, 0
+        where the rate sent nothing; out = a tensor [rows][>= n_sym * steps][2] with contiguous rows is written in place, nothing behind
+        a row's steps touched.  The rule on the host: dvbt.dvbt_deinterleave_numpy.  A decoder of rate 1/2 only.  Nothing is copied to
+        the host."""
+        from . import dvbt
+        t = self.torch
+        m = dvbt._mode(mode)
+        v, rate = dvbt._check(v, rate)
+        if self.R != 2:
+            raise ValueError("the DVB-T front end feeds a rate 1/2 decoder")
+        rows, n_sym, stride = _args.dvbt_symbols(symbols, self._soft_dtype, m.n_max * v)
+        steps = n_sym * dvbt.dvbt_steps_per_symbol(m, v, rate)
+        first, p_in, p_out = 0, None, None
+        if isinstance(parity, (tuple, list)):
+            p_in, p_out = parity
+            _args.dense(p_in, t.int32, rows, "parity[0]"), _args.dense(p_out, t.int32, rows, "parity[1]")
+            if p_in.data_ptr() == p_out.data_ptr():
+                raise ValueError("the two parity counters must be distinct tensors")
+        else:
+            first = int(parity) & 1
+        if out is None:
+            out = self._empty((rows, steps, 2) if symbols.dim() == 3 else (steps, 2), self._soft_dtype)
+        pitch = _args.dvbt_out(out, self._soft_dtype, rows, steps)
+        if rows == 0 or n_sym == 0:
+            return out
+        _lib.check(_lib.load().vit_hip_dvbt_deinterleave_batch(self._handle._h, _ptr(symbols), stride, rows, n_sym, m.index, v, rate, first,
+                                                               _ptr(p_in), _ptr(p_out), _ptr(out), pitch, self._stream()))
+        return out
+
     def dab_deinterleave(self, frames, n_frames=None, source_index=None, hist=None, fill=None, n_received: int = None, out=None):
         """the DAB time de-interleaver fused with depuncturing, in front of decode (vit_hip_dab_deinterleave_batch; ETSI EN 300 401
         clauses 12 and 11).  frames: the received soft bits, a CUDA tensor of the decoder's symbol dtype [rows][max_frames][>= n] (or
