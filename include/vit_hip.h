@@ -1141,7 +1141,7 @@ int vit_hip_chainback_host(vit_hip_handle h, const uint64_t* decisions, size_t L
  * two synchronisations and four staging copies around 0.3 ms of trellis.  The lazy pair leaves the rows where they were made:
  *   vit_hip_update_host_lazy    runs n_steps steps like vit_hip_update_host, but stores their decision rows as rows [first_row,
  *       first_row + n_steps) of the handle's DEVICE row store instead of returning them (the store keeps earlier rows; a handle has
- *       one frame's rows, as a ViterbiDecoder_Core has one m_decisions).  K <= 7: symbols are read straight from pinned host-mapped
+ *       one frame's rows, as a ViterbiDecoder_Core has one m_decisions).  K <= 7 (and K = 8, 9 with R <= 4): symbols are read straight from pinned host-mapped
  *       memory, metrics / renormalisation sum come back through it, and the host polls a completion word instead of synchronising
  *       the stream.  When the call COMPLETES a frame of `speculate_bits` decoded bits (first_row + n_steps == speculate_bits + K-1;
  *       0 = never) the same launch also chains back those bits from `speculate_end_state` and keeps the bytes;
@@ -1154,6 +1154,20 @@ int vit_hip_update_host_lazy(vit_hip_handle h, void* metrics_inout, const void* 
                              size_t speculate_bits, size_t speculate_end_state, uint64_t* renorm_sum_out);
 int vit_hip_chainback_host_lazy(vit_hip_handle h, size_t L, size_t end_state, uint8_t* bytes_out);
 int vit_hip_fetch_decisions_host(vit_hip_handle h, size_t first_row, size_t n_rows, uint64_t* decisions_out);
+
+/* Which kernels serve the single-decoder routes above (eager pair and frame route alike) for this handle's (K, R):
+ *   "single-frame in-place (K = 7)"   K = 7, R <= 4: one wavefront walks the trellis in place, two helper wavefronts beside it
+ *   "single-frame lane == state"      K <= 7, R <= 8 otherwise: one wavefront, one state per lane
+ *   "single-frame wide (K = 8, 9)"    K = 8, 9 with R <= 4: one wavefront, lane == state mod 64, two or four states per lane
+ *   "PLAN_LDS on one frame"           everything else (R >= 5 at K = 8, 9; K >= 10): the general LDS kernels, two workgroup barriers
+ *                                     per trellis step -- the note says which limit the code is beyond
+ * VIT_HIP_HOST_ROUTE_LDS forces the last family at any K (results are bit for bit those of the others: an A/B inside one process);
+ * VIT_HIP_HOST_ROUTE_AUTO (the default) gives the choice back.  Rows already in the device row store stay valid across a change.
+ * The note is one line of text in thread-local storage, valid until the thread's next call, like vit_hip_plan_note's. */
+#define VIT_HIP_HOST_ROUTE_AUTO 0
+#define VIT_HIP_HOST_ROUTE_LDS 1
+const char* vit_hip_host_route_note(vit_hip_handle h);
+int vit_hip_set_host_route(vit_hip_handle h, int route);
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,13 @@ public:
     vit_hip_handle hip_handle() const { return m_hip; }
     // the kernel plan behind this decoder and, where it is the slow compatibility plan, how to get a faster one (vit_hip_plan_note)
     const char* plan_note() const { return vit_hip_plan_note(m_hip); }
+    // the kernels behind THIS object's update() / chainback() (vit_hip_host_route_note), and the switch that puts the general LDS
+    // plan there instead (VIT_HIP_HOST_ROUTE_LDS; VIT_HIP_HOST_ROUTE_AUTO gives the choice back): same results, an A/B in one process
+    const char* host_route_note() const { return vit_hip_host_route_note(m_hip); }
+    void set_host_route(int route) {
+        flush_pending();
+        viterbi_hip_detail::require_ok(vit_hip_set_host_route(m_hip, route), "vit_hip_set_host_route");
+    }
 
     // ---- deferred streaming (used by ViterbiDecoder_HIP::update) -------------------------------------------------------------
     // The reference's streaming callers hand update() the R symbols of ONE trellis step at a time

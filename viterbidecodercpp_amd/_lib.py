@@ -16,6 +16,7 @@ OK = 0
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_RUNTIME, ERR_NO_DEVICE, ERR_WORKSPACE = -1, -2, -3, -4, -5
 PLAN_AUTO, PLAN_LDS, PLAN_REG, PLAN_LDS2 = 0, 1, 2, 3
 PLAN_NAMES = {PLAN_LDS: "lds", PLAN_REG: "reg", PLAN_LDS2: "lds2"}
+HOST_ROUTE_AUTO, HOST_ROUTE_LDS = 0, 1          # vit_hip_set_host_route: the kernels behind ONE decoder object's update() / chainback()
 
 # every symbol include/vit_hip.h declares
 EXPORTS = [
@@ -29,6 +30,7 @@ EXPORTS = [
     "vit_hip_pipeline_wait_event", "vit_hip_get_kernel_resources", "vit_hip_list_kernels",
     "vit_hip_chainback_batch_ex", "vit_hip_pipeline_create_ex", "vit_hip_pipeline_get_schedule_v2", "vit_hip_plan_note",
     "vit_hip_precompile", "vit_hip_update_host_lazy", "vit_hip_chainback_host_lazy", "vit_hip_fetch_decisions_host",
+    "vit_hip_host_route_note", "vit_hip_set_host_route",
     "vit_hip_tail_biting_workspace_bytes", "vit_hip_decode_tail_biting_batch",
     "vit_hip_stream_workspace_bytes", "vit_hip_decode_stream",
     "vit_hip_streams_workspace_bytes", "vit_hip_decode_streams",
@@ -136,6 +138,9 @@ def load():
     L.vit_hip_update_host_lazy.argtypes = [vp, vp, vp, sz, sz, sz, sz, C.POINTER(C.c_uint64)]
     L.vit_hip_chainback_host_lazy.argtypes = [vp, sz, sz, vp]
     L.vit_hip_fetch_decisions_host.argtypes = [vp, sz, sz, vp]
+    L.vit_hip_host_route_note.argtypes = [vp]
+    L.vit_hip_host_route_note.restype = C.c_char_p
+    L.vit_hip_set_host_route.argtypes = [vp, i32]
     L.vit_hip_precompile.argtypes = [i32, i32, C.POINTER(C.c_uint32), i32, C.c_char_p, C.c_char_p, sz]
     L.vit_hip_blob_bytes.restype = sz
     L.vit_hip_blob_bytes.argtypes = [i32, i32, i32, i32]

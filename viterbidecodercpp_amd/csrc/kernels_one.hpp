@@ -22,6 +22,8 @@
 //     with a cross-lane minimum (__shfl_xor).
 // The chainback kernel copies the frame's decision rows into LDS with all 64 lanes and chases 64 SEGMENTS of the frame at once,
 // each from a speculated top state that a sequential pass then verifies (one_chainback_kernel below): exact, and microseconds.
+// K = 8, 9 with R <= 4 (IS-95A, CDMA 2000) run the same scheme with two or four states per lane: one_update_wide_body,
+// one_chainback_body<NRW>, one_frame_wide_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -509,7 +511,7 @@ template <int R, int SHIFT>
 __global__ void __launch_bounds__(192) one_update7_kernel(OneUpdateArgs a) { one_update7_body<R, SHIFT>(a); }
 
 struct OneChainbackArgs {
-    const uint64_t* decisions;   // [L + K-1] words
+    const uint64_t* decisions;   // [L + K-1] rows of one word (K <= 7), of N / 64 words (K = 8, 9)
     uint8_t* out;                // [ceil(L/8)]
     uint32_t end_state;
     uint32_t L;
@@ -524,11 +526,18 @@ struct OneChainbackArgs {
 // segment whose guess was wrong is chased again from the true state (never on real data; random decision rows do it, and the
 // tests feed some).  Results are those of the sequential chase in every case; the kernel takes microseconds instead of the third
 // of a millisecond a 8192-step dependent chain costs one wavefront.
+// K = 8, 9 (one_chainback_body<NRW>, NRW = 2, 4 words per row): the same passes over rows of NRW words -- row[state >> 6] >>
+// (state & 63), core.h:64-66,:226 -- with the chunk cut to 8192 / NRW rows, so that the staged rows stay 64 KiB, and a
+// longer warm-up (survivors of 256 states take longer to merge; a guess that is wrong is repaired either way).
 constexpr int ONE_CB_CHUNK = 8192;       // rows staged per pass (64 KiB of LDS)
 constexpr int ONE_CB_WARM = 64;          // speculative steps in front of a segment
+constexpr int ONE_CB_WARM_WIDE = 96;     // ... of a K = 8, 9 frame
+template <int NRW = 1>
 __device__ __forceinline__ void one_chainback_body(const OneChainbackArgs& a, uint64_t* one_rows) {
-    // one_rows: [ONE_CB_CHUNK + 64 + 8] rows (one pad row per segment), then the chunk's output bytes
-    uint8_t* const obytes = (uint8_t*)(one_rows + ONE_CB_CHUNK + 64 + 8);
+    constexpr int CHUNK = ONE_CB_CHUNK / NRW;
+    constexpr int WARM = NRW == 1 ? ONE_CB_WARM : ONE_CB_WARM_WIDE;
+    // one_rows: [CHUNK + 64 + 8] rows of NRW words (one pad row per segment), then the chunk's output bytes
+    uint8_t* const obytes = (uint8_t*)(one_rows + (CHUNK + 64 + 8) * NRW);
     const int lane = threadIdx.x & 63;
     const int TSB = a.K - 1;
     const int ignore = TSB < 8 ? TSB : 8;                   // ViterbiTracebackBuffer::get_layout (core.h:129-149)
@@ -539,19 +548,34 @@ __device__ __forceinline__ void one_chainback_body(const OneChainbackArgs& a, ui
     while (j > 0) {
         // the chunk covers decoded bits [j0, j), j0 a multiple of 8.  Inside it rows are addressed top-down: q = n8 - 1 - (bit - j0)
         // with n8 = the chunk's bits rounded up to whole bytes (the frame's top byte may be partial: q then starts above 0).
-        const size_t j0 = j > (size_t)ONE_CB_CHUNK ? ((j - ONE_CB_CHUNK + 7) & ~(size_t)7) : 0;
+        const size_t j0 = j > (size_t)CHUNK ? ((j - CHUNK + 7) & ~(size_t)7) : 0;
         const uint32_t n = (uint32_t)(j - j0), n8 = (n + 7u) & ~7u, q_first = n8 - n;
         // 64 segments of `seg` rows (whole bytes), lane i: q in [i seg, (i+1) seg); LDS slot of row q = q + q / seg -- one pad row
         // per segment, so that the lanes' row streams (seg rows apart) start two banks apart instead of in the same bank
         const uint32_t seg = ((n8 / 8u + 63u) / 64u) * 8u;
         const uint32_t nseg = (n8 + seg - 1u) / seg;
-        for (uint32_t q = q_first + (uint32_t)lane; q < n8; q += 64) one_rows[q + q / seg] = a.decisions[j0 + (size_t)(n8 - 1u - q) + (size_t)TSB];
+        if constexpr (NRW == 1) {
+            for (uint32_t q = q_first + (uint32_t)lane; q < n8; q += 64) one_rows[q + q / seg] = a.decisions[j0 + (size_t)(n8 - 1u - q) + (size_t)TSB];
+        } else {
+            // consecutive lanes take consecutive words of a row
+            for (uint32_t x = (uint32_t)lane; x < n * NRW; x += 64) {
+                const uint32_t q = q_first + x / NRW, w = x % NRW;
+                one_rows[(size_t)(q + q / seg) * NRW + w] = a.decisions[(j0 + (size_t)(n8 - 1u - q) + (size_t)TSB) * NRW + w];
+            }
+        }
         __syncthreads();
         auto step = [&](uint32_t& reg, uint32_t slot) __attribute__((always_inline)) {
-            const uint64_t w = one_rows[slot];
-            const uint32_t state = reg >> shift_state;
-            const uint32_t bit = (uint32_t)(w >> state) & 1u;
-            reg = (reg >> 1) | (bit << (total_bits - 1));
+            if constexpr (NRW == 1) {
+                const uint64_t w = one_rows[slot];
+                const uint32_t state = reg >> shift_state;
+                const uint32_t bit = (uint32_t)(w >> state) & 1u;
+                reg = (reg >> 1) | (bit << (total_bits - 1));
+            } else {
+                const uint32_t state = reg >> shift_state;
+                const uint64_t w = one_rows[(size_t)slot * NRW + (state >> 6)];
+                const uint32_t bit = (uint32_t)(w >> (state & 63u)) & 1u;
+                reg = (reg >> 1) | (bit << (total_bits - 1));
+            }
         };
         // chase segment `sidx` from `top_state`, writing its bytes where `writer`; returns the state below it.  Bit (relative to j0)
         // of row q: n8 - 1 - q; a byte is complete when that is a multiple of 8
@@ -571,7 +595,7 @@ __device__ __forceinline__ void one_chainback_body(const OneChainbackArgs& a, ui
             if (lane > 0) {
                 // warm-up: from state 0, up to WARM rows above the segment's top (all inside the chunk)
                 const uint32_t qt = (uint32_t)lane * seg;
-                const uint32_t warm = qt - q_first < (uint32_t)ONE_CB_WARM ? qt - q_first : (uint32_t)ONE_CB_WARM;
+                const uint32_t warm = qt - q_first < (uint32_t)WARM ? qt - q_first : (uint32_t)WARM;
                 uint32_t reg = 0;
                 for (uint32_t q = qt - warm; q < qt; ++q) step(reg, q + q / seg);
                 guess = (reg >> shift_state) & smask;
@@ -598,9 +622,16 @@ __device__ __forceinline__ void one_chainback_body(const OneChainbackArgs& a, ui
     }
 }
 
+#ifndef VIT_ONE_WIDE_UNIT      // (no template: emitted by every unit that sees it -- vit_host.hip launches it, vit_host_wide.hip leaves it out)
 __global__ void __launch_bounds__(64) one_chainback_kernel(OneChainbackArgs a) {
     extern __shared__ uint64_t one_rows_smem[];
     one_chainback_body(a, one_rows_smem);
+}
+#endif
+template <int NRW>
+__global__ void __launch_bounds__(64) one_chainback_wide_kernel(OneChainbackArgs a) {
+    extern __shared__ uint64_t one_rows_smem[];
+    one_chainback_body<NRW>(a, one_rows_smem);
 }
 
 // The FRAME route of the header-level drop-in (vit_hip_update_host_lazy): update() and the chainback() that will follow it in ONE
@@ -647,7 +678,222 @@ __global__ void __launch_bounds__(192) one_frame7_kernel(OneFrameArgs a) {
     if ((threadIdx.x & 63) == 0) __hip_atomic_store(a.done, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- K = 8, 9 (128, 256 states), R <= 4: lane == state mod 64, N / 64 metrics per lane ----
+// one_update_body with NR = N / 64 states per lane, in the reference's order again: lane l holds states l + 64 r (r < NR), so that
+// __ballot of register r's decision IS word r of the reference's row (state s: word s / 64, bit s % 64; scalar.h:131-134).
+// New state s = l + 64 r comes out of butterfly j = s >> 1 = (l >> 1) + 32 r, whose predecessors j and j + N/2 both live in lane
+// (l >> 1) + 32 (r & 1), in registers r >> 1 and (r >> 1) + NR/2.  The metrics are therefore kept PACKED, register q with register
+// q + NR/2 above it (K = 9: m0 | m2 << 16 and m1 | m3 << 16; K = 8: m0 | m1 << 16): a fetched dword is already the pair (old[j],
+// old[j + N/2]), NR ds_bpermute_b32 -- the packed dwords from each of the lanes l >> 1 and (l >> 1) + 32 -- bring all 2 NR predecessor
+// metrics of the lane's NR new states, and one v_pk_add_u16 forms both candidates of a state.  The input bit of every state of a lane
+// is l & 1, so the `max_error - e` constants stay per lane; the branch pattern (the rotate counts) is per register.  Symbol pairs per
+// group of steps read with v_readlane, the late threshold test, parked decision words and the coalesced row-group store are those
+// of one_update_body; a group is 32 steps (a step here is the work of two to four steps there: half the unrolled code).
+// Renormalisation: state 0 is lane 0's register 0 (the low half of packed register 0); the minimum runs over the lane's halves
+// first, then across the lanes.
+struct OneUpdateWideArgs {
+    const uint8_t* symbols;      // device: n_steps * R soft_t of ONE frame
+    size_t sym_total_bytes;
+    uint64_t* decisions;         // [n_steps][N / 64] 64-bit words, rows of THIS call
+    void* metrics_io;            // [N] error_t: read (no reset) and written
+    uint64_t* renorm_sum;        // [1]
+    const uint16_t* pattern;     // [H] bit i = (branch_table[i][j] == high)
+    int32_t K, n_steps;
+    DevConfig cfg;
+    int32_t metrics_in_args;     // frame route: the metrics to start from are metrics_in (device domain), metrics_io is only written
+    uint16_t metrics_in[256];
+};
+
+typedef unsigned short one_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t one_pk_add(uint32_t x, uint32_t y) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(one_u16x2, x) + __builtin_bit_cast(one_u16x2, y));
+}
+__device__ __forceinline__ uint32_t one_pk_sub(uint32_t x, uint32_t y) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(one_u16x2, x) - __builtin_bit_cast(one_u16x2, y));
+}
+
+template <int K, int R, int SHIFT>
+__device__ __forceinline__ void one_update_wide_body(const OneUpdateWideArgs& a) {
+    static_assert((K == 8 || K == 9) && R >= 1 && R <= 4, "two or four states per lane");
+    constexpr int N = 1 << (K - 1), NR = N / 64, NP = NR / 2;    // states, states per lane, packed registers per lane
+    constexpr int GRP = 32;                                      // steps per group
+    const int lane = threadIdx.x & 63;
+    const int jl = lane >> 1;                                    // butterfly of register r: jl + 32 r
+    const int addr[2] = {4 * jl, 4 * (jl + 32)};                 // ds_bpermute byte addresses of the two predecessor lanes
+
+    // per register and polynomial: 16 where the butterfly expects `high`, else 0 (the rotate count of one_update_body)
+    uint32_t rot[NR][R];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const uint32_t p = a.pattern[jl + 32 * r];
+#pragma unroll
+        for (int i = 0; i < R; ++i) rot[r][i] = ((p >> i) & 1u) ? 16u : 0u;
+    }
+
+    auto metric_in = [&](int s) __attribute__((always_inline)) -> uint32_t {
+        if (a.metrics_in_args) return a.metrics_in[s];
+        if (SHIFT) return (uint32_t)(((const uint8_t*)a.metrics_io)[s]) << 8;
+        return ((const uint16_t*)a.metrics_io)[s];
+    };
+    uint32_t P[NP];                                              // states lane + 64 q (low half) and lane + 64 (q + NP) (high half)
+#pragma unroll
+    for (int q = 0; q < NP; ++q) P[q] = metric_in(lane + 64 * q) | (metric_in(lane + 64 * (q + NP)) << 16);
+
+    // lane l (mod 32) forms (|low - y_i| | |high - y_i| << 16) of step t0 + l, the step loop reads step k's out of lane k
+    auto symbol_pairs = [&](int t0, uint32_t (&ap)[R]) __attribute__((always_inline)) {
+        const int t = t0 + (lane & (GRP - 1));
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            int32_t y = 0;
+            if (t < a.n_steps) {
+                if (SHIFT) y = (int32_t)(int16_t)(uint16_t)((uint32_t)((const uint8_t*)a.symbols)[(size_t)t * R + i] << 8);
+                else y = (int32_t)((const int16_t*)a.symbols)[(size_t)t * R + i];
+            }
+            ap[i] = (uint32_t)abs_soft(a.cfg.low, y) | ((uint32_t)abs_soft(a.cfg.high, y) << 16);
+        }
+    };
+
+    uint64_t acc = 0;
+    uint32_t w_lo[NR], w_hi[NR];                                 // the decision row this lane parks: step (32 k + lane) of the call
+#pragma unroll
+    for (int r = 0; r < NR; ++r) w_lo[r] = w_hi[r] = 0;
+    const uint32_t threshold = a.cfg.threshold;
+    const uint32_t c1 = ((uint32_t)a.cfg.max_error + 1u) & 0xFFFFu;
+    const bool b_in = (lane & 1) != 0;                           // input bit of every next-state of this lane
+    // (xa | xb << 16) = ((e | e << 16) ^ XX) + CC in both halves: xa = b ? max_error - e : e, xb the other way round (one_update_body)
+    const uint32_t XX = b_in ? 0x0000FFFFu : 0xFFFF0000u, CC = b_in ? c1 : c1 << 16;
+
+    uint32_t m_state0 = 0xFFFFFFFFu;                             // state 0's metric after the last step run; -1: no step yet
+    auto renormalise = [&]() __attribute__((always_inline)) {
+        uint32_t mn = 0xFFFFu;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const uint32_t lo = P[q] & 0xFFFFu, hi = P[q] >> 16;
+            const uint32_t m2 = lo < hi ? lo : hi;
+            mn = m2 < mn ? m2 : mn;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)mn, off);
+            mn = o < mn ? o : mn;
+        }
+#pragma unroll
+        for (int q = 0; q < NP; ++q) P[q] = one_pk_sub(P[q], mn | (mn << 16));
+        acc += (uint64_t)(mn >> SHIFT);
+    };
+    // register r's pair (old[j], old[j + N/2]): packed register r >> 1 of lane (l >> 1) + 32 (r & 1)
+    auto fetch = [&](uint32_t (&f)[NR]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) f[r] = (uint32_t)__builtin_amdgcn_ds_bpermute(addr[r & 1], (int)P[r >> 1]);
+    };
+
+    uint32_t ap_next[R];
+    symbol_pairs(0, ap_next);
+    for (int t0 = 0; t0 < a.n_steps; t0 += GRP) {
+        uint32_t ap[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) ap[i] = ap_next[i];
+        symbol_pairs(t0 + GRP, ap_next);                         // in flight across this group's steps
+        const int nb = a.n_steps - t0 < GRP ? a.n_steps - t0 : GRP;
+        auto group = [&](auto partial_c) __attribute__((always_inline)) {
+        one_static_for<GRP>([&](auto kc) __attribute__((always_inline)) {
+            constexpr int k = decltype(kc)::value;
+            if (!decltype(partial_c)::value || k < nb) {
+            // ---- the dependent chain of the step: the predecessors' metrics ----
+            uint32_t f[NR];
+            fetch(f);
+            // the PREVIOUS step's threshold test, behind the issue of this step's fetches (one_update_body)
+            if (__builtin_expect((int32_t)m_state0 >= (int32_t)threshold, 0)) {
+                renormalise();
+                fetch(f);
+            }
+            uint32_t pair[R];
+#pragma unroll
+            for (int i = 0; i < R; ++i) pair[i] = (uint32_t)__builtin_amdgcn_readlane((int)ap[i], k);
+            uint32_t nm[NR];
+            one_static_for<NR>([&](auto rc) __attribute__((always_inline)) {
+                constexpr int r = decltype(rc)::value;
+                // ... while they travel: e of the register's butterfly, doubled into both halves, and the candidates' addends
+                uint32_t e = 0;
+#pragma unroll
+                for (int i = 0; i < R; ++i) e += __builtin_amdgcn_alignbit(pair[i], pair[i], rot[r][i]);
+                const uint32_t x = one_pk_add(__builtin_amdgcn_perm(e, e, 0x01000100u) ^ XX, CC);
+                const uint32_t c = one_pk_add(f[r], x);                            // old[j] + xa | (old[j + N/2] + xb) << 16
+                const uint32_t m0 = c & 0xFFFFu, m1 = c >> 16;
+                const bool d = m0 > m1;                                            // strict: tie -> 0        :123-124
+                nm[r] = m0 < m1 ? m0 : m1;                                         // d ? m1 : m0             :127-128
+                const uint64_t word = __ballot(d);                                 // word r of the row       :131-134
+                uint32_t &wl = w_lo[r], &wh = w_hi[r];
+                asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(wl) : "s"((uint32_t)word), "n"(k));   // (s_nop: see one_update7_body)
+                asm("v_writelane_b32 %0, %1, %2" : "+v"(wh) : "s"((uint32_t)(word >> 32)), "n"(k));
+            });
+#pragma unroll
+            for (int q = 0; q < NP; ++q) P[q] = nm[q] | (nm[q + NP] << 16);
+            m_state0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)P[0]) & 0xFFFFu;   // tested behind the NEXT step's fetches
+            }
+        });
+        };
+        if (nb == GRP) group(std::false_type{});      // whole groups: no per-step test
+        else group(std::true_type{});
+        // the group's rows: one coalesced store (8 NR bytes per lane)
+        if (lane < nb) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) a.decisions[((size_t)t0 + (size_t)lane) * NR + r] = ((uint64_t)w_hi[r] << 32) | w_lo[r];
+        }
+    }
+    if ((int32_t)m_state0 >= (int32_t)threshold) renormalise();      // the last step's test
+
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const uint32_t lo = P[q] & 0xFFFFu, hi = P[q] >> 16;
+        if (SHIFT) {
+            ((uint8_t*)a.metrics_io)[lane + 64 * q] = (uint8_t)(lo >> 8);
+            ((uint8_t*)a.metrics_io)[lane + 64 * (q + NP)] = (uint8_t)(hi >> 8);
+        } else {
+            ((uint16_t*)a.metrics_io)[lane + 64 * q] = (uint16_t)lo;
+            ((uint16_t*)a.metrics_io)[lane + 64 * (q + NP)] = (uint16_t)hi;
+        }
+    }
+    if (lane == 0) a.renorm_sum[0] = acc;
+}
+
+template <int K, int R, int SHIFT>
+__global__ void __launch_bounds__(64) one_update_wide_kernel(OneUpdateWideArgs a) { one_update_wide_body<K, R, SHIFT>(a); }
+
+// the frame route at K = 8, 9: one_frame_kernel with the wide bodies
+struct OneFrameWideArgs {
+    OneUpdateWideArgs u;
+    OneChainbackArgs c;
+    int32_t do_chainback;
+    uint32_t seq;
+    uint32_t* done;              // host-mapped
+};
+template <int K, int R, int SHIFT>
+__global__ void __launch_bounds__(64) one_frame_wide_kernel(OneFrameWideArgs a) {
+    extern __shared__ uint64_t one_rows_smem[];
+    one_update_wide_body<K, R, SHIFT>(a.u);
+    if (a.do_chainback) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");   // the rows this wavefront stored are read back by the same wavefront
+        __syncthreads();
+        one_chainback_body<(1 << (K - 1)) / 64>(a.c, one_rows_smem);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");           // system scope: everything above is visible to the host ...
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) __hip_atomic_store(a.done, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // ... before this
+}
+
 constexpr size_t one_chainback_lds_bytes() { return ((size_t)ONE_CB_CHUNK + 64 + 8) * 8 + ONE_CB_CHUNK / 8 + 8; }
+constexpr size_t one_chainback_wide_lds_bytes(int NRW) { return ((size_t)ONE_CB_CHUNK / NRW + 64 + 8) * NRW * 8 + ONE_CB_CHUNK / NRW / 8 + 8; }
 inline bool one_supported(int K, int R) { return K >= 2 && K <= 7 && R >= 1 && R <= 8; }
+inline bool one_wide_supported(int K, int R) { return (K == 8 || K == 9) && R >= 1 && R <= 4; }
+
+// The wide kernels are instantiated and launched by a unit of their own, vit_host_wide.hip (2 x 4 x 2 update and frame kernels of
+// 32 unrolled steps each: beside the K <= 7 kernels in vit_host.hip they would double the longest compile of the library's build);
+// vit_host.hip calls these.  hipFuncSetAttribute per launch, as every launcher of the library does.
+#pragma GCC visibility push(hidden)
+hipError_t one_wide_launch_update(int K, int R, int shift, const OneUpdateWideArgs& a, hipStream_t st);
+hipError_t one_wide_launch_frame(int K, int R, int shift, const OneFrameWideArgs& a, hipStream_t st);
+hipError_t one_wide_launch_chainback(int words_per_row, const OneChainbackArgs& a, hipStream_t st);
+#pragma GCC visibility pop
 
 }  // namespace vit

@@ -1,7 +1,8 @@
 // vit_host.hip -- the routes of ONE decoder object whose state lives on the host between calls: vit_hip_update_host /
 // vit_hip_chainback_host (every call stages through pinned memory) and the frame route (vit_hip_update_host_lazy /
-// vit_hip_chainback_host_lazy / vit_hip_fetch_decisions_host: rows kept on the device, one launch per frame).  K <= 7 runs the
-// single-frame kernels of kernels_one.hpp, which only this unit launches; larger codes the LDS plan on one frame (vit_hip.hip).
+// vit_hip_chainback_host_lazy / vit_hip_fetch_decisions_host: rows kept on the device, one launch per frame).  K <= 7, and K = 8, 9
+// with R <= 4, run the single-frame kernels of kernels_one.hpp, which only this unit launches; larger codes -- and any code after
+// vit_hip_set_host_route(h, VIT_HIP_HOST_ROUTE_LDS) -- the LDS plan on one frame (vit_hip.hip).
 #include "vit_internal.hpp"
 #include "kernels_one.hpp"
 
@@ -85,7 +86,19 @@ int one_launch_frame(int R, const OneFrameArgs& a, hipStream_t st) {
     });
 }
 
-// K <= 7: rows staged through LDS by the whole wavefront, one lane chases (kernels_one.hpp); the end state is a kernel argument
+// (K = 8, 9 with R <= 4: the launchers of the wide kernels are vit_host_wide.hip's, declared in kernels_one.hpp)
+
+// which kernels serve this handle's single-decoder routes (vit_hip_host_route_note names them)
+enum HostFamily { HOST_ONE7, HOST_ONE, HOST_WIDE, HOST_LDS };
+HostFamily host_family(vit_hip_handle h) {
+    if (h->host_route == VIT_HIP_HOST_ROUTE_LDS) return HOST_LDS;
+    if (one_update7_supported(h->K, h->R)) return HOST_ONE7;
+    if (one_supported(h->K, h->R)) return HOST_ONE;
+    if (one_wide_supported(h->K, h->R)) return HOST_WIDE;
+    return HOST_LDS;
+}
+
+// K <= 9: rows staged through LDS by the whole wavefront, 64 segments chased at once (kernels_one.hpp); the end state is a kernel argument
 int one_launch_chainback(vit_hip_handle h, const uint64_t* d_rows, size_t L, size_t end_state, uint8_t* d_out) {
     if (L > 0xFFFFFFF0ull) return fail(VIT_HIP_ERR_INVALID_ARG, "L too large");
     OneChainbackArgs ca{};
@@ -96,6 +109,10 @@ int one_launch_chainback(vit_hip_handle h, const uint64_t* d_rows, size_t L, siz
     ca.K = h->K;
     // per launch, like every other > 64 KiB launcher of the library: the attribute belongs to the CURRENT device's function object
     // (a process-wide `static` would opt in only the device of the first caller: a decoder on device 1..7 launched without it)
+    if (h->W > 1) {
+        VIT_HIP_CHECK(one_wide_launch_chainback(h->W, ca, h->stream));
+        return VIT_HIP_OK;
+    }
     VIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(one_chainback_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)one_chainback_lds_bytes()));
     hipLaunchKernelGGL(one_chainback_kernel, dim3(1), dim3(64), one_chainback_lds_bytes(), h->stream, ca);
@@ -105,7 +122,7 @@ int one_launch_chainback(vit_hip_handle h, const uint64_t* d_rows, size_t L, siz
 
 // chainback of the one frame whose rows are on the device: the single-frame kernel, or the LDS plan with the end state in d_end_state
 int chainback_one_frame(vit_hip_handle h, const uint64_t* d_rows, size_t L, size_t end_state, uint8_t* d_out, uint32_t* d_end_state) {
-    if (one_supported(h->K, h->R)) return one_launch_chainback(h, d_rows, L, end_state, d_out);
+    if (host_family(h) != HOST_LDS) return one_launch_chainback(h, d_rows, L, end_state, d_out);
     const uint32_t es = (uint32_t)end_state;
     VIT_HIP_CHECK(hipMemcpyAsync(d_end_state, &es, 4, hipMemcpyHostToDevice, h->stream));
     return lds_chainback(h, d_rows, 1, L, d_out, d_end_state, h->stream);
@@ -161,8 +178,22 @@ int vit_hip_update_host(vit_hip_handle h, void* metrics_inout, const void* symbo
     if (rc != VIT_HIP_OK) return rc;
     uint64_t* d_dec = (uint64_t*)(s.base + s.in_b);
     // streaming state lives on the host between calls: one frame.  K <= 7 (at most 64 states): the one-wavefront latency kernel
-    // (kernels_one.hpp: lane == state, metrics in a register, ~100 clocks per step); larger codes: the LDS plan on one frame
-    if (one_supported(h->K, h->R)) {
+    // (kernels_one.hpp: lane == state, metrics in a register, ~100 clocks per step); K = 8, 9 with R <= 4: its wide sibling (two or
+    // four states per lane); larger codes, and every code under VIT_HIP_HOST_ROUTE_LDS: the LDS plan on one frame
+    const HostFamily family = host_family(h);
+    if (family == HOST_WIDE) {
+        OneUpdateWideArgs oa{};
+        oa.symbols = s.d_sym();
+        oa.sym_total_bytes = s.sym_bytes;
+        oa.decisions = d_dec;
+        oa.metrics_io = s.base;
+        oa.renorm_sum = s.d_rs();
+        oa.pattern = h->d_pattern;
+        oa.K = h->K;
+        oa.n_steps = (int)n_steps;
+        oa.cfg = h->cfg;
+        VIT_HIP_CHECK(one_wide_launch_update(h->K, h->R, h->shift, oa, h->stream));
+    } else if (family != HOST_LDS) {
         OneUpdateArgs oa{};
         oa.symbols = s.d_sym();
         oa.sym_total_bytes = s.sym_bytes;
@@ -236,8 +267,10 @@ int vit_hip_update_host_lazy(vit_hip_handle h, void* metrics_inout, const void* 
     if (rc != VIT_HIP_OK) return rc;
     const size_t sym_bytes = n_steps * (size_t)h->R * (size_t)h->soft_bytes;
     const size_t met_bytes = (size_t)h->N * (size_t)h->error_bytes;
-    if (!one_supported(h->K, h->R)) {
-        // K > 7: the LDS plan on one frame, as vit_hip_update_host runs it -- but the rows go straight into the device row store
+    const HostFamily family = host_family(h);
+    if (family == HOST_LDS) {
+        // no single-frame kernel (or none wanted): the LDS plan on one frame, as vit_hip_update_host runs it -- but the rows go
+        // straight into the device row store
         UpdateStage s;
         rc = stage_update_in(h, metrics_inout, symbols, n_steps, 0, s);
         if (rc != VIT_HIP_OK) return rc;
@@ -259,35 +292,46 @@ int vit_hip_update_host_lazy(vit_hip_handle h, void* metrics_inout, const void* 
     VIT_HIP_CHECK(hipHostGetDevicePointer(&dm_v, h->h_map, 0));
     uint8_t* dm = (uint8_t*)dm_v;
     memcpy(hm + sym_off, symbols, sym_bytes);
-    OneFrameArgs fa{};
-    fa.u.symbols = dm + sym_off;
-    fa.u.sym_total_bytes = sym_bytes;
-    fa.u.decisions = h->d_rows + first_row;                  // W == 1 here
-    fa.u.metrics_io = dm + met_off;
-    fa.u.renorm_sum = (uint64_t*)(dm + 64);
-    fa.u.pattern = h->d_pattern;
-    fa.u.K = h->K;
-    fa.u.n_steps = (int)n_steps;
-    fa.u.cfg = h->cfg;
-    fa.u.metrics_in_args = 1;
-    for (int s = 0; s < 64; ++s) {
-        const int t = s & (h->N - 1);
-        fa.u.metrics_in[s] = h->error_bytes == 1 ? (uint16_t)((uint32_t)((const uint8_t*)metrics_inout)[t] << 8) : ((const uint16_t*)metrics_inout)[t];
-    }
-    fa.do_chainback = spec ? 1 : 0;
-    fa.c.decisions = h->d_rows;
-    fa.c.out = dm + out_off;
-    fa.c.end_state = (uint32_t)speculate_end_state;
-    fa.c.L = (uint32_t)speculate_bits;
-    fa.c.K = h->K;
-    fa.seq = ++h->seq ? h->seq : ++h->seq;                   // never 0
-    fa.done = (uint32_t*)dm;
+    const uint32_t seq = ++h->seq ? h->seq : ++h->seq;       // never 0
+    // OneFrameArgs and OneFrameWideArgs differ in the number of start metrics they carry (64 / 256)
+    auto fill = [&](auto& fa) {
+        fa.u.symbols = dm + sym_off;
+        fa.u.sym_total_bytes = sym_bytes;
+        fa.u.decisions = h->d_rows + first_row * (size_t)h->W;
+        fa.u.metrics_io = dm + met_off;
+        fa.u.renorm_sum = (uint64_t*)(dm + 64);
+        fa.u.pattern = h->d_pattern;
+        fa.u.K = h->K;
+        fa.u.n_steps = (int)n_steps;
+        fa.u.cfg = h->cfg;
+        fa.u.metrics_in_args = 1;
+        for (int s = 0; s < (int)(sizeof(fa.u.metrics_in) / sizeof(fa.u.metrics_in[0])); ++s) {
+            const int t = s & (h->N - 1);
+            fa.u.metrics_in[s] = h->error_bytes == 1 ? (uint16_t)((uint32_t)((const uint8_t*)metrics_inout)[t] << 8) : ((const uint16_t*)metrics_inout)[t];
+        }
+        fa.do_chainback = spec ? 1 : 0;
+        fa.c.decisions = h->d_rows;
+        fa.c.out = dm + out_off;
+        fa.c.end_state = (uint32_t)speculate_end_state;
+        fa.c.L = (uint32_t)speculate_bits;
+        fa.c.K = h->K;
+        fa.seq = seq;
+        fa.done = (uint32_t*)dm;
+    };
     volatile uint32_t* done = (volatile uint32_t*)hm;
-    if ((h->shift ? one_launch_frame<8>(h->R, fa, h->stream) : one_launch_frame<0>(h->R, fa, h->stream)) != 0)
-        return fail(VIT_HIP_ERR_RUNTIME, "frame kernel launch failed");
+    int launched;
+    if (family == HOST_WIDE) {
+        OneFrameWideArgs fa{};
+        fill(fa);
+        launched = one_wide_launch_frame(h->K, h->R, h->shift, fa, h->stream) == hipSuccess ? 0 : -1;
+    } else {
+        OneFrameArgs fa{};
+        fill(fa);
+        launched = h->shift ? one_launch_frame<8>(h->R, fa, h->stream) : one_launch_frame<0>(h->R, fa, h->stream);
+    }
+    if (launched != 0) return fail(VIT_HIP_ERR_RUNTIME, "frame kernel launch failed");
     // the kernel's last act is a system-scope release store of seq into the control word: poll it (a stream synchronisation costs more
     // than the whole chainback); a kernel that never gets there shows up in the stream's status
-    const uint32_t seq = fa.seq;
     for (uint64_t spins = 0; __atomic_load_n(done, __ATOMIC_ACQUIRE) != seq; ++spins) {
         if ((spins & 0xFFFFu) == 0xFFFFu) {
             const hipError_t q = hipStreamQuery(h->stream);
@@ -341,6 +385,41 @@ int vit_hip_chainback_host_lazy(vit_hip_handle h, size_t L, size_t end_state, ui
     VIT_HIP_CHECK(hipMemcpyAsync(h->h_stage, base, out_bytes, hipMemcpyDeviceToHost, h->stream));
     VIT_HIP_CHECK(hipStreamSynchronize(h->stream));
     memcpy(bytes_out, h->h_stage, out_bytes);
+    return VIT_HIP_OK;
+}
+
+const char* vit_hip_host_route_note(vit_hip_handle h) {
+    if (!h) return "NULL handle";
+    thread_local std::string note;
+    char head[48];
+    snprintf(head, sizeof(head), "K=%d R=%d: ", h->K, h->R);
+    note = head;
+    switch (host_family(h)) {
+        case HOST_ONE7:
+            note += "single-frame in-place (K = 7): one wavefront walks the trellis in place, two helper wavefronts make its branch metrics "
+                    "and its decision rows (csrc/kernels_one.hpp: one_update7_kernel, one_frame7_kernel)";
+            break;
+        case HOST_ONE:
+            note += "single-frame lane == state: one wavefront, one state per lane (csrc/kernels_one.hpp: one_update_kernel, one_frame_kernel)";
+            break;
+        case HOST_WIDE:
+            note += "single-frame wide (K = 8, 9): one wavefront, lane == state mod 64, " + std::to_string(h->N / 64) +
+                    " states per lane (csrc/kernels_one.hpp: one_update_wide_kernel, one_frame_wide_kernel)";
+            break;
+        default:
+            note += "PLAN_LDS on one frame (the general LDS kernels: two workgroup barriers per trellis step)";
+            if (h->host_route == VIT_HIP_HOST_ROUTE_LDS) note += "; forced by vit_hip_set_host_route(h, VIT_HIP_HOST_ROUTE_LDS)";
+            else if (h->K >= 10) note += "; the single-frame kernels serve K <= 9: K >= 10";
+            else note += "; the single-frame kernels serve R <= 4 at K = 8, 9: R >= 5";
+    }
+    return note.c_str();
+}
+
+int vit_hip_set_host_route(vit_hip_handle h, int route) {
+    if (!h) return fail(VIT_HIP_ERR_INVALID_ARG, "NULL handle");
+    if (route != VIT_HIP_HOST_ROUTE_AUTO && route != VIT_HIP_HOST_ROUTE_LDS)
+        return fail(VIT_HIP_ERR_INVALID_ARG, "route must be VIT_HIP_HOST_ROUTE_AUTO or VIT_HIP_HOST_ROUTE_LDS");
+    h->host_route = route;
     return VIT_HIP_OK;
 }
 

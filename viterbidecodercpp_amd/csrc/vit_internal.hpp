@@ -7,6 +7,7 @@
 //                    calls as declared below (kernels_tb.hpp, kernels_stream.hpp)
 //   vit_pipeline.hip vit_hip_pipeline_* and its schedule rules (no kernel of its own)
 //   vit_host.hip     the single-decoder host route and the frame route (kernels_one.hpp)
+//   vit_host_wide.hip  that header's kernels for K = 8, 9 and their launchers, which vit_host.hip calls: beside it for the build's sake
 //   vit_tools.hip    synth, bit-error count, shader clock, kernel listing, precompile, RCCL table broadcast (kernels_synth.hpp)
 //   vit_encode.hip   the encoder on the caller's bytes and the re-encoded channel symbol error count (kernels_enc.hpp)
 //   vit_sync.hip     node synchronisation: the streams of a set of alignment hypotheses and their ranking, around the C ABI's own
@@ -76,6 +77,7 @@ struct vit_hip_decoder {
     uint32_t seq = 0;               // the value the next frame kernel stores into the control word when it is done
     bool spec_valid = false;        // the decoded bytes in h_map are those of chainback(spec_bits, spec_end) over the rows in d_rows
     size_t spec_bits = 0, spec_end = 0, spec_off = 0;
+    int host_route = VIT_HIP_HOST_ROUTE_AUTO;   // vit_hip_set_host_route: AUTO, or the LDS plan on one frame at any K
 };
 
 namespace vit {

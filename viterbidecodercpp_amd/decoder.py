@@ -178,6 +178,16 @@ class ViterbiDecoder_Core:
     def rows_on_device(self) -> int:
         return self._dev_end - self._dev_begin
 
+    def host_route_note(self) -> str:
+        """vit_hip_host_route_note: the kernel family behind this object's update() / chainback(), in one line"""
+        return _lib.load().vit_hip_host_route_note(self._handle._h).decode()
+
+    def set_host_route(self, route: int):
+        """_lib.HOST_ROUTE_LDS puts the general LDS plan behind update() / chainback() at any K (same results: an A/B inside one
+        process); _lib.HOST_ROUTE_AUTO, the default, gives the choice back"""
+        self.flush_pending()
+        _lib.check(_lib.load().vit_hip_set_host_route(self._handle._h, route))
+
     def set_traceback_length(self, traceback_length: int):
         self.flush_pending()
         self.fetch_device_rows()
