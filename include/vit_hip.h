@@ -1116,6 +1116,95 @@ int vit_hip_dvbt_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t i
                                     void* d_symbols_out /* [rows][>= n_sym * steps][2] soft_t */, size_t out_row_stride,
                                     vit_hip_stream_t stream);
 
+/* ---- IS-95A forward traffic channel, rate set 1: de-interleave, combine the repetitions, pick the rate ---------------------------------
+ * The forward traffic channel of TIA/EIA-95 sends 20 ms frames at 9600, 4800, 2400 or 1200 bit/s through the K = 9, R = 1/2 code, repeats
+ * every code symbol 1, 2, 4 or 8 times to 384 symbols, block-interleaves them and scrambles them with the decimated long code -- and sends no
+ * rate field.  The receiver combines the repetitions under all four hypotheses, decodes all four and chooses by the frame quality indicator
+ * (CRC) and the re-encoded symbol error rate.  These calls stand around vit_hip_decode_batch and vit_hip_crc_batch on a handle of K = 9,
+ * R = 2; the de-interleave and the decision do not depend on the polynomials.  The constants are written from memory of TIA/EIA-95
+ * 7.1.3; what is stated HERE is the rule.
+ * POLYNOMIALS.  In this ABI bit k of a polynomial taps the input of k steps ago.  The stock code "CDMA IS-95A" (491, 369) is 0o753, 0o561
+ * read literally under that convention; the standard's figures read with the leftmost bit of 753 on the encoder INPUT -- as 133 / 171 are
+ * read for 802.11 -- are the reciprocal set (431, 285) = 0o657, 0o435, which the GENERIC K = 9 kernels serve.
+ * Hypothesis h = 0 .. 3, repetition r = 2^h:   rate   bits before the tail L_h   info bits   CRC over the info bits          steps S_h = L_h + 8   bytes
+ *                                      h = 0  9600   184                        172         (12, 0xF13, 0xFFF, 0)          192                   23
+ *                                      h = 1  4800   88                         80          (8, 0x9B, 0xFF, 0)             96                    11
+ *                                      h = 2  2400   40                         40          none                           48                    5
+ *                                      h = 3  1200   16                         16          none                           24                    2
+ * Transmit side: info bits, the CRC MSB-first (vit_hip_crc_batch's codes), 8 zero tail bits; encoded, c[2 n + o] = polynomial o of step n;
+ * repeated, s[q r + j] = c[q] for j < r: 384 symbols at every rate; interleaved, y[i] = s[A(i)] with A(i) = 64 (i mod 6) + BRO6(i div 6),
+ * BRO6 the reversal of 6 bits; scrambled, y[i] negated where scramble bit i of the frame is 1.  A(0 .. 7) = 0, 64, 128, 192, 256, 320, 32,
+ * 96 (the standard's table, 1-based, starts 1, 65, 129, 193, 257, 321, 33, 97); the inverse is i(a) = 6 BRO6(a mod 64) + a div 64, so s[1] =
+ * y[192], s[2] = y[96], s[64] = y[1], s[383] = y[383].
+ *
+ * vit_hip_is95_deinterleave_batch: descrambles, de-interleaves and combines for the four hypotheses in one launch; soft_t is the handle's
+ * symbol type.
+ *   - input: frame f is 384 soft_t at d_in + f * in_frame_stride (elements; 0 => 384; a non-zero stride is at least 384);
+ *   - d_scramble (may be NULL: nothing is negated): 48 bytes a frame at d_scramble + f * scramble_frame_stride bytes (0 => ONE 48-byte mask
+ *     for the whole batch; a non-zero stride is at least 48), bit i of a frame, for received symbol i, being bit 7 - i%8 of byte i/8;
+ *   - d_out[h], h = 0 .. 3, any of them NULL but not all: the [frames][S_h][2] buffer vit_hip_decode_batch reads with L = L_h;
+ *   - out_h[f][q] = clamp(round_shift(sum over j < 2^h of sg(f, i) in[f][i]), i = i(q 2^h + j)) for q < 2 S_h: sg = -1 where the scramble bit
+ *     is set, else +1; int32 arithmetic, -(-32768) is 32768; round_shift(x) = (x + ((1 << shift) >> 1)) >> shift (arithmetic); clamp to
+ *     [clamp_lo, clamp_hi] -- the rounding and clamp of vit_hip_lte_rate_dematch_batch.  An erasure (0 where the midpoint of the handle's
+ *     soft_decision_high / low is 0) stays one under negation and adds nothing: that is how a caller removes the punctured power-control
+ *     symbols.
+ * Every element of every non-NULL output is always written; nothing outside a frame's 384 elements and 48 mask bytes is read.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_in or d_out, all four outputs
+ * NULL, a handle with R != 2, shift > 15, clamp_lo > clamp_hi or either outside soft_t, d_in not aligned to soft_t, an output not aligned to
+ * 4 bytes, a non-zero in_frame_stride below 384 or scramble_frame_stride below 48, frames or a stride at or above 2^31 - 1, outputs that
+ * overlap each other, the input or the mask.  frames = 0 returns VIT_HIP_OK with no work.
+ *
+ * vit_hip_is95_channel_errors_batch: for every hypothesis h with d_bytes[h] != NULL, d_errors[h] and d_compared[h] receive exactly what
+ * vit_hip_channel_errors_batch(h, d_symbols[h], 0, d_bytes[h], bytes_frame_stride[h], frames, L_h, VIT_HIP_ENCODE_TAIL, NULL, d_errors[h],
+ * d_compared[h], stream) writes -- but the up to eight counter arrays are zeroed by ONE kernel of the call's own, not by memsets: 1 + up to
+ * 4 launches and no memset node in a captured graph.  Memset nodes of a replayed graph have been seen not to write zeros on this runtime
+ * (HISTORY.md, the marker search; with eight of them in one graph the counts of this chain came back wrong from the second replay on), so
+ * a chain meant for a graph counts through this call.  Host arrays of four; bytes_frame_stride NULL or an entry 0 => 23, 11, 5, 2.
+ * Errors: VIT_HIP_ERR_UNSUPPORTED when vit_hip_info.table_is_linear is 0; VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs
+ * untouched, for a NULL handle or array, a handle that is not K = 9, R = 2, all four d_bytes NULL, a present hypothesis without d_symbols,
+ * d_errors or d_compared, d_symbols not aligned to soft_t or a count array not to 4 bytes, a non-zero stride that is too small, frames or a
+ * stride at or above 2^31 - 1, count arrays that overlap each other or an input.  frames = 0 returns VIT_HIP_OK with no work.
+ *
+ * vit_hip_is95_rate_decide_batch: the decision and the compaction.  All arrays of pointers and scalars are HOST arrays; what they point to
+ * is on the device.
+ *   - d_bytes[h]: the decoded bytes of hypothesis h, frame f at d_bytes[h] + f * bytes_frame_stride[h] (bytes_frame_stride NULL or an entry
+ *     0 => 23, 11, 5, 2; a non-zero stride is at least that), bit t of a frame being bit 7 - t%8 of byte t/8.  NULL takes hypothesis h out
+ *     of the contest; not all four;
+ *   - d_errors[h], d_compared[h], uint32 [frames]: what vit_hip_channel_errors_batch wrote for d_out[h] and d_bytes[h] with L = L_h and
+ *     VIT_HIP_ENCODE_TAIL; d_syndrome[0], d_syndrome[1], uint32 [frames]: what vit_hip_crc_batch wrote with rows = 1, first_bit = 0, n_bits =
+ *     172 / 80 and the codes above.  Required for a present hypothesis, not read for an absent one;
+ *   - hypothesis h PASSES for frame f when it is present, h >= 2 or its syndrome is 0, compared_h > 0 and errors_h * ser_den <= compared_h *
+ *     max_ser_num[h] (64-bit products; ser_den > 0).  rate = the passing h with the smallest errors_h / compared_h, compared by 64-bit
+ *     cross-multiplication, the lower h on a tie; 4 where nothing passes: an erased frame.  A transparent default, not a policy: the
+ *     standard prescribes no rule and every input stays with the caller;
+ *   - d_decision[f] = {rate, info_bits (172, 80, 40, 16; 0 at rate 4), errors, compared of the winner (0 at rate 4)};
+ *   - d_info + f * info_stride (0 => 22; a non-zero stride is at least 22): all 22 bytes are always written; the first info_bits bits are
+ *     those of the winner's bytes, every bit behind them is 0 -- byte 21 of a full-rate frame keeps its top 4 bits.
+ * Whatever the count and syndrome memory holds, nothing outside the frames' own bytes and entries is read.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, array, d_decision or d_info, all
+ * four d_bytes NULL, a present hypothesis without its counts (or, h < 2, its syndrome), ser_den = 0, a non-zero stride that is too small,
+ * d_decision or a count array not aligned to 4 bytes, frames or a stride at or above 2^31 - 1, an output that overlaps the other or an
+ * input.  frames = 0 returns VIT_HIP_OK with no work.
+ * Batch calls like the others: the de-interleave and the decision each enqueue ONE kernel on `stream`, the error counts up to five, none a
+ * memset; they allocate nothing, need no workspace, synchronise nothing, read the handle only for its device, soft_t, K and R (the error
+ * counts: its polynomials too), and can be captured into a hipGraph: de-interleave, 4 decodes, the error counts, 2 CRCs and the decision
+ * are one graph.
+ * Out of scope: rate set 2 (14400 and its puncturing); the long-code generator itself (the caller supplies the decimated bits);
+ * power-control bit extraction; sync and paging channels (continuous encoding: vit_hip_decode_stream); the reverse link (other interleaver,
+ * 64-ary orthogonal modulation); cdma2000 radio configurations 3 and up (R = 1/4 with puncturing); any rate-decision policy beyond the
+ * rule above. */
+typedef struct vit_hip_is95_decision { uint32_t rate, info_bits, errors, compared; } vit_hip_is95_decision;
+int vit_hip_is95_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in_frame_stride, size_t frames, const uint8_t* d_scramble,
+                                    size_t scramble_frame_stride, unsigned shift, int clamp_lo, int clamp_hi,
+                                    void* const d_out[4] /* [frames][S_h][2] soft_t each, or NULL */, vit_hip_stream_t stream);
+int vit_hip_is95_channel_errors_batch(vit_hip_handle h, const void* const d_symbols[4], const uint8_t* const d_bytes[4],
+                                      const size_t bytes_frame_stride[4], size_t frames, uint32_t* const d_errors[4],
+                                      uint32_t* const d_compared[4], vit_hip_stream_t stream);
+int vit_hip_is95_rate_decide_batch(vit_hip_handle h, const uint8_t* const d_bytes[4], const size_t bytes_frame_stride[4],
+                                   const uint32_t* const d_errors[4], const uint32_t* const d_compared[4],
+                                   const uint32_t* const d_syndrome[2], size_t frames, const uint32_t max_ser_num[4], uint32_t ser_den,
+                                   vit_hip_is95_decision* d_decision, uint8_t* d_info, size_t info_stride, vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

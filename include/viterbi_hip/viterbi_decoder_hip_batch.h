@@ -339,6 +339,39 @@ public:
                                               d_symbols_out, out_row_stride, stream),
               "vit_hip_dvbt_deinterleave_batch");
     }
+    // The IS-95A forward traffic channel, rate set 1 (vit_hip_is95_deinterleave_batch / vit_hip_is95_rate_decide_batch), a decoder of K = 9,
+    // R = 2.  is95_deinterleave descrambles (d_scramble: 48 bytes a frame MSB-first at scramble_frame_stride bytes, 0: one mask for all;
+    // nullptr: off), undoes the 384-symbol block interleaver and adds the repetitions under the four rate hypotheses in one launch:
+    // d_out[h] (nullptr: not wanted; not all four) receives [frames][S_h][2], S_h = 192, 96, 48, 24, which decode reads with total_bits =
+    // 184, 88, 40, 16; sums in int32, rounded by (x + ((1 << shift) >> 1)) >> shift, clamped to [clamp_lo, clamp_hi].  is95_rate_decide
+    // picks, per frame, the hypothesis with the lowest errors / compared among those that are present (d_bytes[h] != nullptr), check
+    // (d_syndrome[h] == 0, h < 2) and keep errors * ser_den <= compared * max_ser_num[h]: d_decision[f] = {rate (4: erased), info_bits,
+    // errors, compared} and 22 info bytes at d_info + f * info_stride (0: 22), zero behind the winner's info bits.  The arrays of
+    // pointers, strides and thresholds are host arrays of four (d_syndrome: two); bytes_frame_stride nullptr: 23, 11, 5, 2.
+    void is95_deinterleave(const soft_t* d_in, size_t frames, soft_t* const d_out[4], const uint8_t* d_scramble = nullptr,
+                           size_t scramble_frame_stride = 0, unsigned shift = 0, int clamp_lo = -127, int clamp_hi = 127,
+                           size_t in_frame_stride = 0, void* stream = nullptr) {
+        void* const out[4] = {d_out[0], d_out[1], d_out[2], d_out[3]};
+        check(vit_hip_is95_deinterleave_batch(m_hip, d_in, in_frame_stride, frames, d_scramble, scramble_frame_stride, shift, clamp_lo,
+                                              clamp_hi, out, stream),
+              "vit_hip_is95_deinterleave_batch");
+    }
+    // the four re-encoded symbol error counts behind one zeroing kernel (vit_hip_is95_channel_errors_batch): what channel_errors writes for
+    // every hypothesis with d_bytes[h] != nullptr, with no memset node in a captured graph
+    void is95_channel_errors(const soft_t* const d_symbols[4], const uint8_t* const d_bytes[4], size_t frames, uint32_t* const d_errors[4],
+                             uint32_t* const d_compared[4], const size_t* bytes_frame_stride = nullptr, void* stream = nullptr) {
+        const void* const sym[4] = {d_symbols[0], d_symbols[1], d_symbols[2], d_symbols[3]};
+        check(vit_hip_is95_channel_errors_batch(m_hip, sym, d_bytes, bytes_frame_stride, frames, d_errors, d_compared, stream),
+              "vit_hip_is95_channel_errors_batch");
+    }
+    void is95_rate_decide(const uint8_t* const d_bytes[4], const uint32_t* const d_errors[4], const uint32_t* const d_compared[4],
+                          const uint32_t* const d_syndrome[2], size_t frames, const uint32_t max_ser_num[4], uint32_t ser_den,
+                          vit_hip_is95_decision* d_decision, uint8_t* d_info, size_t info_stride = 0,
+                          const size_t* bytes_frame_stride = nullptr, void* stream = nullptr) {
+        check(vit_hip_is95_rate_decide_batch(m_hip, d_bytes, bytes_frame_stride, d_errors, d_compared, d_syndrome, frames, max_ser_num,
+                                             ser_den, d_decision, d_info, info_stride, stream),
+              "vit_hip_is95_rate_decide_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -204,3 +204,78 @@ def dvbt_out(x, dtype, rows, steps):
     if x.dim() == 3 and rows > 1 and x.stride(0) < 2 * steps:
         raise ValueError("the rows of out overlap")
     return int(x.stride(0)) // 2 if x.dim() == 3 and rows > 1 else int(x.shape[-2])
+
+
+def is95_symbols(x, dtype, scramble):
+    """(frames, row stride in elements, mask stride in bytes) of an is95_deinterleave call: symbols by the rule of wifi_rows with 384
+    elements a frame; scramble None, a dense uint8 tensor [48] (stride 0: one mask for the batch) or [frames][>= 48] by that rule"""
+    import torch
+    frames, stride = wifi_rows(x, dtype, 384, "symbols")
+    if scramble is None:
+        return frames, stride, 0
+    if scramble.dim() == 1:
+        dense(scramble, torch.uint8, 48, "scramble")
+        return frames, stride, 0
+    sframes, sstride = wifi_rows(scramble, torch.uint8, 48, "scramble")
+    if sframes != frames:
+        raise ValueError(f"scramble must be [48] or [{frames}][>= 48]")
+    return frames, stride, sstride
+
+
+def is95_outputs(out, dtype, frames):
+    """the four outputs of an is95_deinterleave call as a tuple: dense tensors of `dtype` with frames * 2 S_h elements, S_h = 192, 96, 48,
+    24, or None where a hypothesis is not wanted -- not all four --, no two of which share storage"""
+    out = tuple(out)
+    if len(out) != 4 or all(x is None for x in out):
+        raise ValueError("out must be four tensors, None where a hypothesis is not wanted, not all None")
+    for h, x in enumerate(out):
+        if x is not None:
+            dense(x, dtype, frames * (384 >> h), f"out[{h}]")
+    spans = sorted((x.data_ptr(), x.data_ptr() + x.numel() * x.element_size()) for x in out if x is not None and x.numel())
+    if any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+        raise ValueError("the outputs must not share storage")
+    return out
+
+
+def is95_decoded(bytes, errors, compared, syndrome):
+    """(frames, the four byte strides) of an is95_rate_decide call: bytes, four uint8 tensors by the rule of wifi_rows with 23, 11, 5 and 2
+    bytes a frame in two dimensions, None for an absent hypothesis (stride 0), not all; for every present one dense int32 [frames] counts
+    in errors and compared and, for the first two, in syndrome (errors None: the counts are not part of the call)"""
+    import torch
+    counted = errors is not None
+    if len(bytes) != 4 or all(b is None for b in bytes) or (counted and (len(errors) != 4 or len(compared) != 4 or len(syndrome) < 2)):
+        raise ValueError("bytes, errors and compared must hold four entries, syndrome two; not every hypothesis may be absent")
+    frames, strides = None, []
+    for h, b in enumerate(bytes):
+        if b is None:
+            strides.append(0)
+            continue
+        n, stride = wifi_rows(b, torch.uint8, (23, 11, 5, 2)[h], f"bytes[{h}]")
+        if b.dim() != 2 or (frames is not None and n != frames):
+            raise ValueError("every hypothesis must hold [frames] rows of bytes")
+        frames = n
+        strides.append(stride)
+        for x, what in (((errors[h], "errors"), (compared[h], "compared")) + (((syndrome[h], "syndrome"),) if h < 2 else ())) if counted else ():
+            if x is None:
+                raise ValueError(f"{what}[{h}] is missing")
+            dense(x, torch.int32, frames, f"{what}[{h}]")
+    return frames, strides
+
+
+def is95_counted(symbols, bytes, errors, compared, dtype, frames):
+    """an is95_channel_errors call: for every hypothesis whose bytes are given, symbols[h] a dense tensor of `dtype` with frames * 2 S_h
+    elements and errors[h], compared[h] dense int32 [frames], no two of the count tensors the same"""
+    import torch
+    if len(symbols) != 4 or len(errors) != 4 or len(compared) != 4:
+        raise ValueError("symbols, errors and compared must hold four entries")
+    seen = set()
+    for h, b in enumerate(bytes):
+        if b is None:
+            continue
+        if symbols[h] is None or errors[h] is None or compared[h] is None:
+            raise ValueError(f"hypothesis {h} needs symbols, errors and compared")
+        dense(symbols[h], dtype, frames * (384 >> h), f"symbols[{h}]")
+        for x, what in ((errors[h], "errors"), (compared[h], "compared")):
+            if dense(x, torch.int32, frames, f"{what}[{h}]").data_ptr() in seen and frames:
+                raise ValueError("the count tensors must be distinct")
+            seen.add(x.data_ptr())

@@ -46,6 +46,7 @@ EXPORTS = [
     "vit_hip_dabplus_sync", "vit_hip_dabplus_au_batch",
     "vit_hip_wifi_deinterleave_batch", "vit_hip_wifi_signal_batch", "vit_hip_wifi_data_batch",
     "vit_hip_dvbt_deinterleave_batch",
+    "vit_hip_is95_deinterleave_batch", "vit_hip_is95_channel_errors_batch", "vit_hip_is95_rate_decide_batch",
 ]
 
 
@@ -192,6 +193,10 @@ def load():
     L.vit_hip_wifi_signal_batch.argtypes = [vp, vp, sz, sz, vp, vp]
     L.vit_hip_wifi_data_batch.argtypes = [vp, vp, sz, sz, sz, vp, sz, sz, vp, sz, vp, vp]
     L.vit_hip_dvbt_deinterleave_batch.argtypes = [vp, vp, sz, sz, sz, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, sz, vp]
+    L.vit_hip_is95_deinterleave_batch.argtypes = [vp, vp, sz, sz, vp, sz, C.c_uint, i32, i32, C.POINTER(vp), vp]
+    L.vit_hip_is95_channel_errors_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(vp), C.POINTER(vp), vp]
+    L.vit_hip_is95_rate_decide_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz,
+                                                 C.POINTER(C.c_uint32), C.c_uint32, vp, vp, sz, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

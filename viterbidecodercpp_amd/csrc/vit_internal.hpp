@@ -31,6 +31,8 @@
 //                    parser, descrambling and the FCS behind it (kernels_wifi.hpp, which takes those device functions likewise)
 //   vit_dvbt.hip     the front of the DVB-T route: the inner de-interleaver (symbol, bit, demultiplexer) fused with depuncturing in front
 //                    of the stream decode (kernels_dvbt.hpp); behind the decode DVB-T is the DVB-S chain of vit_dvb.hip
+//   vit_is95.hip     the IS-95A forward traffic channel around the K = 9 decode: descrambling, block de-interleaver and the combining of
+//                    the repetitions under the four rate hypotheses in front, the blind rate decision behind (kernels_is95.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -756,6 +756,88 @@ class BatchDecoder(_OuterChain):
                                                                _ptr(p_in), _ptr(p_out), _ptr(out), pitch, self._stream()))
         return out
 
+    def is95_deinterleave(self, symbols, scramble=None, shift: int = 0, clamp=None, out=None, want=(True, True, True, True)):
+        """the IS-95A forward traffic channel in front of decode (vit_hip_is95_deinterleave_batch): long-code descrambling, the 384-symbol
+        block de-interleaver and the combining of the repetitions under the four rate hypotheses, in one launch.  symbols: a CUDA tensor
+        of the decoder's symbol dtype [frames][>= 384] with contiguous rows (or one frame), a view with a larger row stride read in
+        place; scramble: uint8 CUDA, the mask packed MSB-first, [48] for the whole batch or [frames][>= 48] with contiguous rows, None:
+        off.  The repetitions are added in int32, rounded by `shift` ((x + ((1 << shift) >> 1)) >> shift) and clamped to `clamp` = (low,
+        high), default the decoder's soft_decision_low / high.  returns four tensors [frames][S_h][2], S_h = 192, 96, 48, 24, which
+        decode reads with L = 184, 88, 40, 16; `want` leaves hypotheses out (None in their place), out = four such tensors (None: not
+        wanted) are written in place; they must not share storage.  The rule on the host: is95.is95_deinterleave_numpy.  A decoder of
+        rate 1/2 only.  Nothing is copied to the host."""
+        from .is95 import IS95_RATE_SET_1
+        shift = int(shift)
+        if self.R != 2:
+            raise ValueError("the IS-95 traffic channel feeds a rate 1/2 decoder")
+        i = self._handle.info
+        lo, hi = (i.soft_decision_low, i.soft_decision_high) if clamp is None else (int(clamp[0]), int(clamp[1]))
+        if not 0 <= shift <= 15 or lo > hi:
+            raise ValueError("shift must be 0 .. 15, clamp = (low, high) with low <= high")
+        frames, stride, sstride = _args.is95_symbols(symbols, self._soft_dtype, scramble)
+        if out is None:
+            out = tuple(self._empty((frames, r.steps, 2), self._soft_dtype) if w else None for r, w in zip(IS95_RATE_SET_1, want))
+        out = _args.is95_outputs(out, self._soft_dtype, frames)
+        if frames == 0:
+            return out
+        at = (C.c_void_p * 4)(*[None if x is None else x.data_ptr() for x in out])
+        _lib.check(_lib.load().vit_hip_is95_deinterleave_batch(self._handle._h, _ptr(symbols), stride, frames, _ptr(scramble), sstride, shift,
+                                                               lo, hi, at, self._stream()))
+        return out
+
+    def is95_channel_errors(self, symbols, bytes, out=None):
+        """the re-encoded symbol error counts of the four IS-95A hypotheses in one call (vit_hip_is95_channel_errors_batch): symbols, the
+        four tensors is95_deinterleave returned, and bytes, what decode returned for them (uint8 [frames][>= 23 / 11 / 5 / 2] with
+        contiguous rows; None: a hypothesis left out).  returns (errors, compared), two lists of four int32 CUDA tensors [frames] (None
+        where left out) that hold what channel_errors(symbols[h], bytes[h], L_h) returns; out = (errors, compared) reuses such lists.
+        The counters are zeroed by a kernel, not by memsets, so a captured graph holds no memset node.  A K = 9, R = 1/2 decoder only.
+        Nothing is copied to the host."""
+        t = self.torch
+        if (self.K, self.R) != (9, 2):
+            raise ValueError("the IS-95 traffic channel needs a K = 9, R = 1/2 decoder")
+        frames, strides = _args.is95_decoded(bytes, None, None, None)
+        if out is None:
+            out = tuple([None if b is None else self._empty((frames,), t.int32) for b in bytes] for _ in range(2))
+        errors, compared = out
+        _args.is95_counted(symbols, bytes, errors, compared, self._soft_dtype, frames)
+        if frames == 0:
+            return errors, compared
+        ptrs = lambda xs: (C.c_void_p * 4)(*[None if x is None or bytes[k] is None else x.data_ptr() for k, x in enumerate(xs)])
+        _lib.check(_lib.load().vit_hip_is95_channel_errors_batch(self._handle._h, ptrs(symbols), ptrs(bytes), (C.c_size_t * 4)(*strides), frames,
+                                                                 ptrs(errors), ptrs(compared), self._stream()))
+        return errors, compared
+
+    def is95_rate_decide(self, bytes, errors, compared, syndrome, max_ser_num, ser_den: int, out=None):
+        """the blind rate decision of the IS-95A forward traffic channel and the winner's info bits (vit_hip_is95_rate_decide_batch).
+        bytes: four uint8 CUDA tensors [frames][>= 23 / 11 / 5 / 2] with contiguous rows, what decode returned for the four outputs of
+        is95_deinterleave, None for a hypothesis out of the contest; errors, compared: four int32 CUDA tensors [frames] each, what
+        channel_errors returned (not read for an absent hypothesis, which may give None); syndrome: two, what crc_check returned with
+        is95.IS95_CRC12 over 172 bits and IS95_CRC8 over 80.  Hypothesis h passes with a zero syndrome (h < 2), compared > 0 and errors *
+        ser_den <= compared * max_ser_num[h]; the passing one with the lowest errors / compared wins, the lower h on a tie.  returns
+        (decision int32 [frames][4] = (rate, info_bits, errors, compared), the uint32 values of the ABI, rate 4 and zeros for an erased
+        frame; info uint8 [frames][22], the winner's info bits, zero behind them); out = (decision, info) reuses those tensors, info
+        rows may be wider.  The rule on the host: is95.is95_rate_decide_numpy.  Nothing is copied to the host."""
+        from .is95 import IS95_INFO_BYTES, IS95_RATE_SET_1
+        t = self.torch
+        frames, strides = _args.is95_decoded(bytes, errors, compared, syndrome)
+        num = [int(n) for n in max_ser_num]
+        if len(num) != 4 or int(ser_den) < 1 or min(num) < 0 or max(num + [int(ser_den)]) > 0xFFFFFFFF:
+            raise ValueError("max_ser_num must be four uint32 values, ser_den 1 .. 2^32 - 1")
+        if out is None:
+            out = (self._empty((frames, 4), t.int32), self._empty((frames, IS95_INFO_BYTES), t.uint8))
+        decision, info = out
+        _args.dense(decision, t.int32, frames * 4, "out[0]")
+        iframes, istride = _args.wifi_rows(info, t.uint8, IS95_INFO_BYTES, "out[1]")
+        if iframes != frames or info.dim() != 2:
+            raise ValueError(f"out[1] must hold [{frames}] rows")
+        if frames == 0:
+            return decision, info
+        ptrs = lambda xs, n: (C.c_void_p * n)(*[None if x is None or bytes[k] is None else x.data_ptr() for k, x in enumerate(xs[:n])])
+        _lib.check(_lib.load().vit_hip_is95_rate_decide_batch(
+            self._handle._h, ptrs(bytes, 4), (C.c_size_t * 4)(*strides), ptrs(errors, 4), ptrs(compared, 4), ptrs(syndrome, 2), frames,
+            (C.c_uint32 * 4)(*num), int(ser_den), _ptr(decision), _ptr(info), istride, self._stream()))
+        return decision, info
+
     def dab_deinterleave(self, frames, n_frames=None, source_index=None, hist=None, fill=None, n_received: int = None, out=None):
         """the DAB time de-interleaver fused with depuncturing, in front of decode (vit_hip_dab_deinterleave_batch; ETSI EN 300 401
         clauses 12 and 11).  frames: the received soft bits, a CUDA tensor of the decoder's symbol dtype [rows][max_frames][>= n] (or
