@@ -8,6 +8,8 @@
 // crc_build_tables, crc_lane, crc_chunk, crc_combine, crc_finish, with the arguments crc_batch_args makes -- and compares both outputs
 // whole with a bit-by-bit restatement of the rule over a 0xA5 fill.  The one part of the kernel body that stays off the host is the
 // __shfl_xor exchange: here the lanes of a group are run one after the other and the partner's register is read from an array.
+// In front of the shapes: the argument rule (crc_invalid) at an accepted call, at every INVALID_ARG case tests/test_gpu_crc.py sends
+// through the library, and at the zero-work cases; every random shape must pass it too.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,9 +73,69 @@ static void run_kernel(const vit::CrcArgs& a) {
     }
 }
 
+// one call of the argument rule: the accepted base call, which a case changes in a field or two
+struct RuleCall {
+    bool handle = true;
+    const vit_hip_crc_params* code;
+    const uint8_t* frames;
+    size_t stride = 8, rows = 2, mf = 3, first = 0, n = 40;
+    const uint32_t *crc, *syn;
+    const char* operator()() const { return vit::crc_invalid(handle, code, frames, stride, rows, mf, first, n, crc, syn); }
+};
+
+#define WANT(set, bad)                                                                      \
+    do {                                                                                    \
+        RuleCall k = base;                                                                  \
+        set;                                                                                \
+        const char* why_ = k();                                                             \
+        if ((why_ != nullptr) != (bad)) { printf("MISMATCH line %d: %s\n", __LINE__, why_ ? why_ : "accepted"); return 1; } \
+    } while (0)
+
+static int arguments() {
+    const size_t rows = 2, mf = 3, stride = 8;
+    std::vector<uint8_t> buf(rows * mf * stride);                                      // heap blocks the rule never reads
+    std::vector<uint32_t> outs(2 * rows * mf + 1);
+    const uint8_t* a = buf.data();
+    const uint32_t *c = outs.data(), *s = c + rows * mf;
+    const vit_hip_crc_params good = {16, 0x1021, 0xFFFF, 0};
+    RuleCall base;
+    base.code = &good; base.frames = a; base.crc = c; base.syn = s;
+    WANT((void)0, false);
+    WANT(k.handle = false, true);
+    WANT(k.code = nullptr, true);
+    WANT(k.frames = nullptr, true);
+    WANT((k.crc = nullptr, k.syn = nullptr), true);
+    static const vit_hip_crc_params codes[] = {{0, 0, 0, 0}, {33, 1, 0, 0}, {8, 0x100, 0, 0}, {8, 1, 0x100, 0}, {8, 1, 0, 0x100}, {31, 0x80000000u, 0, 0}};
+    for (const vit_hip_crc_params& p : codes) WANT(k.code = &p, true);
+    WANT(k.stride = 6, true);                                                           // 40 + 16 bits need 7 bytes, 40 alone 5
+    WANT(k.n = 49, true);
+    WANT(k.first = 9, true);
+    WANT((k.stride = 4, k.syn = nullptr), true);
+    WANT(k.syn = c, true);                                                              // the outputs on each other, on the frames
+    WANT(k.syn = c + rows * mf - 1, true);
+    WANT(k.crc = (const uint32_t*)a, true);
+    WANT(k.syn = (const uint32_t*)(a + rows * mf * stride - 4), true);
+    WANT(k.crc = (const uint32_t*)((uintptr_t)a - 4 * rows * mf + 1), true);
+    WANT(k.crc = (const uint32_t*)((uintptr_t)a - 4 * rows * mf), false);               // right in front of them
+    WANT(k.rows = (size_t)1 << 31, true);
+    WANT(k.mf = (size_t)1 << 31, true);
+    WANT((k.rows = ((size_t)1 << 31) - 1, k.mf = ((size_t)1 << 31) - 1, k.crc = nullptr), true);
+    WANT(k.n = (size_t)1 << 32, true);
+    WANT(k.first = (size_t)1 << 32, true);
+    WANT(k.stride = 7, false);                                                          // the edges that pass
+    WANT((k.stride = 5, k.syn = nullptr), false);
+    WANT((k.stride = 0, k.n = 48), false);
+    WANT(k.rows = 0, false);                                                            // no work
+    WANT(k.mf = 0, false);
+    WANT((k.rows = 0, k.stride = 6), true);                                             // ... still refuses what needs no shape
+    WANT((k.mf = 0, k.handle = false), true);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int shapes = argc > 1 ? atoi(argv[1]) : 600;
     rng_state = argc > 2 ? strtoull(argv[2], nullptr, 0) : 1;
+    if (arguments()) return 1;
     static const uint64_t edges[] = {0, 1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 128, 129, 136, 240, 256, 257, 264, 512, 520, 1024, 1032,
                                      2048, 2056, 4096, 4104, 8904, 32771};
     uint32_t seen_logG = 0;
@@ -117,6 +179,10 @@ int main(int argc, char** argv) {
         if (d_crc) memset(d_crc, 0xA5, N * sizeof(uint32_t));
         if (d_syn) memset(d_syn, 0xA5, N * sizeof(uint32_t));
 
+        if (const char* why = vit::crc_invalid(true, &c, frames, stride_arg, rows, max_frames, first_bit, n_bits, d_crc, d_syn)) {
+            printf("MISMATCH shape %d refused: %s\n", it, why);
+            return 1;
+        }
         const vit::CrcArgs a = vit::crc_batch_args(c, frames, stride_arg, rows, max_frames, n_frames, first_bit, n_bits, d_crc, d_syn);
         seen_logG |= 1u << a.logG;
         run_kernel(a);

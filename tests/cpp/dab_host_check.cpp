@@ -7,6 +7,8 @@
 // (the elements in front of an output that starts off a dword boundary are poisoned under the address sanitizer), fills the count, fill
 // and map memory with values of every size, runs every thread of the grid through the kernels' own thread functions, and compares every
 // element of every output with a literal restatement of the rule over a 0x5A fill.
+// In front of them: both argument rules (dab_deinterleave_invalid, dab_descramble_invalid) at an accepted call, at every INVALID_ARG
+// case tests/test_gpu_dab.py sends through the library, and at the zero-work cases.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -176,6 +178,134 @@ static int descramble_shape(int it) {
     return bad;
 }
 
+// one call of either argument rule: the accepted base call, which a case changes in a field or two
+struct DeintCall {
+    bool handle = true;
+    size_t sb = 2;
+    const void* d_in;
+    size_t rs = 0, fs = 0, rows = 2, mf = 4;
+    const uint32_t* nfr;
+    size_t n = 32;
+    const int32_t* idx;
+    size_t spf = 40;
+    const void* hist;
+    const uint32_t* fill;
+    size_t hs = 0;
+    const void* out;
+    const uint32_t* n_out;
+    const void* hist_out;
+    const uint32_t* fill_out;
+    const char* operator()() const {
+        return vit::dab_deinterleave_invalid(handle, sb, d_in, rs, fs, rows, mf, nfr, n, idx, spf, hist, fill, hs, out, n_out, hist_out, fill_out);
+    }
+};
+struct DescrCall {
+    bool handle = true;
+    const uint8_t* d_in;
+    size_t s = 0, rows = 2, mf = 4;
+    const uint32_t* nfr;
+    size_t bits = 90;
+    const uint8_t* out;
+    size_t os = 0;
+    const char* operator()() const { return vit::dab_descramble_invalid(handle, d_in, s, rows, mf, nfr, bits, out, os); }
+};
+
+#define WANT(base, set, bad)                                                                \
+    do {                                                                                    \
+        auto k = base;                                                                      \
+        set;                                                                                \
+        const char* why_ = k();                                                             \
+        if ((why_ != nullptr) != (bad)) { printf("MISMATCH line %d: %s\n", __LINE__, why_ ? why_ : "accepted"); return 1; } \
+    } while (0)
+
+static int arguments() {
+    const size_t n = 32, mf = 4, rows = 2, spf = 40, H = vit::DAB_H;
+    std::vector<int16_t> big(4096), out(rows * mf * spf), hist_out(rows * H * n);       // heap blocks the rules never read
+    std::vector<uint32_t> cnts(8);
+    std::vector<int32_t> idx(spf);
+    const int16_t *d_in = big.data(), *d_hist = big.data() + 512;
+    const uint32_t *n_out = cnts.data(), *fill_out = n_out + 2, *fill_in = n_out + 4, *n_frames = n_out + 6;
+    auto plus = [](const void* p, size_t bytes) { return (const void*)((const uint8_t*)p + bytes); };
+    DeintCall g;
+    g.d_in = d_in; g.nfr = n_frames; g.idx = idx.data(); g.hist = d_hist; g.fill = fill_in;
+    g.out = out.data(); g.n_out = n_out; g.hist_out = hist_out.data(); g.fill_out = fill_out;
+    WANT(g, (void)0, false);
+    WANT(g, k.handle = false, true);
+    WANT(g, k.d_in = nullptr, true);
+    WANT(g, k.out = nullptr, true);
+    WANT(g, k.n_out = nullptr, true);
+    WANT(g, k.hist_out = nullptr, true);
+    WANT(g, k.fill_out = nullptr, true);
+    WANT(g, k.fill = nullptr, true);                                                     // a history without its fill
+    WANT(g, (k.hist = nullptr, k.fill = nullptr, k.nfr = nullptr), false);               // the optional ones absent
+    WANT(g, k.n = 0, true);
+    WANT(g, k.spf = 0, true);
+    WANT(g, k.fs = n - 1, true);                                                         // strides
+    WANT(g, k.rs = mf * n - 1, true);
+    WANT(g, (k.fs = n + 1, k.rs = mf * (n + 1) - 1), true);
+    WANT(g, k.hs = H * n - 1, true);
+    WANT(g, k.idx = nullptr, true);                                                      // the identity needs spf == n
+    WANT(g, (k.idx = nullptr, k.spf = n + 1), true);
+    WANT(g, (k.idx = nullptr, k.spf = n), false);
+    WANT(g, k.n = (size_t)1 << 28, true);
+    WANT(g, k.spf = (size_t)1 << 32, true);
+    WANT(g, k.d_in = plus(d_in, 1), true);                                               // alignment
+    WANT(g, k.out = plus(out.data(), 1), true);
+    WANT(g, k.hist = plus(d_hist, 1), true);
+    WANT(g, k.hist_out = plus(hist_out.data(), 1), true);
+    WANT(g, k.idx = (const int32_t*)plus(idx.data(), 2), true);
+    WANT(g, k.n_out = (const uint32_t*)plus(n_out, 2), true);
+    WANT(g, k.nfr = (const uint32_t*)plus(n_frames, 1), true);
+    WANT(g, (k.sb = 1, k.d_in = plus(d_in, 1), k.hist = plus(d_hist, 1)), false);        // soft8: any address
+    WANT(g, k.out = d_in, true);                                                         // overlaps
+    WANT(g, k.out = d_hist, true);
+    WANT(g, k.out = hist_out.data(), true);
+    WANT(g, k.out = idx.data(), true);
+    WANT(g, k.hist_out = d_in, true);
+    WANT(g, k.hist_out = d_hist, true);
+    WANT(g, k.hist_out = idx.data(), true);
+    WANT(g, k.n_out = n_frames, true);
+    WANT(g, k.n_out = fill_in, true);
+    WANT(g, k.fill_out = n_frames, true);
+    WANT(g, k.fill_out = fill_in, true);
+    WANT(g, k.fill_out = n_out, true);
+    WANT(g, k.out = d_hist + rows * H * n, false);                                       // right behind the history
+    WANT(g, k.out = d_hist + rows * H * n - 1, true);
+    WANT(g, k.rows = (size_t)1 << 31, true);                                             // counts
+    WANT(g, (k.mf = (size_t)1 << 31, k.fs = n), true);
+    WANT(g, (k.rows = (size_t)1 << 20, k.mf = (size_t)1 << 20), true);
+    WANT(g, (k.rows = (size_t)1 << 13, k.mf = (size_t)1 << 14, k.spf = (size_t)1 << 5), true);
+    WANT(g, k.rows = 0, false);                                                          // no work
+    WANT(g, k.mf = 0, false);
+    WANT(g, (k.rows = 0, k.n = 0), true);                                                // ... still refuses what needs no shape
+
+    std::vector<uint8_t> frames(rows * mf * 12), dout(rows * mf * 12);
+    DescrCall d;
+    d.d_in = frames.data(); d.nfr = n_frames; d.out = dout.data();
+    WANT(d, (void)0, false);
+    WANT(d, k.handle = false, true);
+    WANT(d, k.d_in = nullptr, true);
+    WANT(d, k.out = nullptr, true);
+    WANT(d, k.bits = ((size_t)1 << 32) - 33, true);
+    WANT(d, k.s = 11, true);
+    WANT(d, k.os = 11, true);
+    WANT(d, k.rows = (size_t)1 << 31, true);
+    WANT(d, k.mf = (size_t)1 << 31, true);
+    WANT(d, (k.rows = (size_t)1 << 16, k.mf = (size_t)1 << 15), true);
+    WANT(d, (k.out = frames.data(), k.os = 13), true);                                   // in place needs equal strides
+    WANT(d, k.out = frames.data(), false);
+    WANT(d, (k.out = frames.data(), k.s = 13, k.os = 13), false);
+    WANT(d, k.out = frames.data() + 1, true);
+    WANT(d, k.out = frames.data() + 12, true);
+    WANT(d, k.out = frames.data() + rows * mf * 12, false);                              // right behind the input
+    WANT(d, k.out = (const uint8_t*)n_frames, true);
+    WANT(d, k.rows = 0, false);                                                          // no work
+    WANT(d, k.mf = 0, false);
+    WANT(d, k.bits = 0, false);
+    WANT(d, (k.rows = 0, k.s = 11), true);                                               // ... still refuses what needs no shape
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int shapes = argc > 1 ? atoi(argv[1]) : 300;
     rng_state = argc > 2 ? strtoull(argv[2], nullptr, 0) : 1;
@@ -184,6 +314,7 @@ int main(int argc, char** argv) {
         if (((vit::DAB_PRBS.w[i / 4] >> (24 - 8 * (i % 4))) & 0xFFu) != first[i]) { printf("MISMATCH: sequence byte %u\n", i); return 1; }
     for (uint32_t j = 0; j < 16; ++j)
         if (vit::dab_delay(j) != DELAY[j] || vit::dab_delay(j + 16) != DELAY[j]) { printf("MISMATCH: delay %u\n", j); return 1; }
+    if (arguments()) return 1;
     for (int it = 0; it < shapes; ++it) {
         if (it % 2 ? deinterleave_shape<int8_t>(it) : deinterleave_shape<int16_t>(it)) return 1;
         if (descramble_shape(it)) return 1;

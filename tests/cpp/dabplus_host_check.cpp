@@ -9,6 +9,8 @@
 // kernel the 64 lanes of a wave run one after the other through its own device functions and the partner's register is read from an
 // array.  Headers are hostile on purpose: random start fields, 0xFFF, decreasing, beyond 110 s, with a Fire code made right afterwards
 // so that the length logic is what keeps the reads inside.  Everything is compared whole with a bit-by-bit restatement.
+// In front of them: both argument rules (dabplus_sync_invalid, dabplus_au_invalid) at an accepted call, at every INVALID_ARG case
+// tests/test_gpu_dabplus.py sends through the library, and at the zero-work cases.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -266,9 +268,110 @@ static int check_au(int it) {
     return bad;
 }
 
+// one call of either argument rule: the accepted base call, which a case changes in a field or two
+struct SyncCall {
+    bool handle = true;
+    const uint8_t* d;
+    size_t rs = 0, fs = 0, fb = 24, rows = 2, mf = 4;
+    const uint32_t* n;
+    unsigned f0 = 0, flags = 0;
+    const uint32_t *hi, *co;
+    const vit_hip_marker_lock* lo;
+    const char* operator()() const { return vit::dabplus_sync_invalid(handle, d, rs, fs, fb, rows, mf, n, f0, flags, hi, co, lo); }
+};
+struct AuCall {
+    bool handle = true;
+    const uint8_t* d;
+    size_t stride = 0, rows = 2, mf = 2;
+    const uint32_t* n;
+    unsigned s = 2;
+    const int32_t* rs = nullptr;
+    const uint32_t* i;
+    const vit_hip_dabplus_au* a;
+    const char* operator()() const { return vit::dabplus_au_invalid(handle, d, stride, rows, mf, n, s, rs, i, a); }
+};
+
+#define WANT(base, set, bad)                                                                \
+    do {                                                                                    \
+        auto k = base;                                                                      \
+        set;                                                                                \
+        const char* why_ = k();                                                             \
+        if ((why_ != nullptr) != (bad)) { printf("MISMATCH line %d: %s\n", __LINE__, why_ ? why_ : "accepted"); return 1; } \
+    } while (0)
+
+static int arguments() {
+    std::vector<uint8_t> buf(4096);                                                      // heap blocks the rules never read
+    std::vector<uint32_t> hits(64), count(64), info(64), nf(2);
+    std::vector<vit_hip_marker_lock> lock(16);
+    std::vector<vit_hip_dabplus_au> au(4 * vit::DABPLUS_SLOTS);
+    std::vector<int32_t> status(4 * 2);
+    auto plus = [](const void* p, size_t bytes) { return (const void*)((const uint8_t*)p + bytes); };
+    SyncCall g;
+    g.d = buf.data(); g.n = nf.data(); g.hi = hits.data(); g.co = count.data(); g.lo = lock.data();
+    WANT(g, (void)0, false);
+    WANT(g, k.handle = false, true);
+    WANT(g, k.d = nullptr, true);
+    WANT(g, k.hi = nullptr, true);
+    WANT(g, k.co = nullptr, true);
+    WANT(g, (k.lo = nullptr, k.n = nullptr), false);                                     // the optional ones absent
+    WANT(g, k.flags = 2, true);
+    WANT(g, k.flags = VIT_HIP_MARKER_ACCUMULATE, false);
+    WANT(g, k.fb = 10, true);
+    WANT(g, k.fb = ((size_t)1 << 31) / 40 + 1, true);
+    WANT(g, k.f0 = 5, true);
+    WANT(g, k.fs = 23, true);                                                            // strides
+    WANT(g, k.rs = 95, true);
+    WANT(g, (k.fs = 24, k.rs = 96), false);
+    WANT(g, k.rows = (size_t)1 << 31, true);
+    WANT(g, k.mf = (size_t)1 << 31, true);
+    WANT(g, k.n = (const uint32_t*)plus(nf.data(), 2), true);                            // alignment
+    WANT(g, k.lo = (const vit_hip_marker_lock*)plus(lock.data(), 2), true);
+    WANT(g, k.co = hits.data(), true);                                                   // overlaps
+    WANT(g, k.co = hits.data() + 2 * vit::DABPLUS_PHASES - 1, true);
+    WANT(g, k.co = hits.data() + 2 * vit::DABPLUS_PHASES, false);
+    WANT(g, k.lo = (const vit_hip_marker_lock*)hits.data(), true);
+    WANT(g, k.hi = (const uint32_t*)buf.data(), true);
+    WANT(g, k.hi = (const uint32_t*)(buf.data() + 2 * 4 * 24 - 4), true);
+    WANT(g, k.hi = (const uint32_t*)(buf.data() + 2 * 4 * 24), false);                   // right behind the frames
+    WANT(g, k.lo = (const vit_hip_marker_lock*)nf.data(), true);
+    WANT(g, k.rows = 0, false);                                                          // no work
+    WANT(g, (k.mf = 0, k.lo = nullptr), false);
+    WANT(g, (k.mf = 0, k.hi = (const uint32_t*)buf.data()), false);                      // no frames: nothing of them to overlap
+    WANT(g, (k.rows = 0, k.f0 = 5), true);                                               // ... still refuses what needs no shape
+
+    AuCall t;
+    t.d = buf.data(); t.n = nf.data(); t.i = info.data(); t.a = au.data();
+    WANT(t, (void)0, false);
+    WANT(t, k.rs = status.data(), false);
+    WANT(t, k.handle = false, true);
+    WANT(t, k.d = nullptr, true);
+    WANT(t, k.i = nullptr, true);
+    WANT(t, k.a = nullptr, true);
+    WANT(t, k.s = 0, true);
+    WANT(t, k.s = 25, true);
+    WANT(t, k.stride = 219, true);
+    WANT(t, k.stride = 220, false);
+    WANT(t, k.rows = (size_t)1 << 31, true);
+    WANT(t, k.mf = (size_t)1 << 31, true);
+    WANT(t, (k.rows = ((size_t)1 << 31) - 1, k.mf = ((size_t)1 << 31) - 1), true);
+    WANT(t, k.i = (const uint32_t*)plus(info.data(), 2), true);                          // alignment
+    WANT(t, k.rs = (const int32_t*)plus(status.data(), 1), true);
+    WANT(t, k.a = (const vit_hip_dabplus_au*)info.data(), true);                         // overlaps
+    WANT(t, k.i = (const uint32_t*)buf.data(), true);
+    WANT(t, k.i = (const uint32_t*)(buf.data() + 3 * 240 + 216), true);
+    WANT(t, k.i = (const uint32_t*)(buf.data() + 3 * 240 + 220), false);                 // right behind the last superframe's data
+    WANT(t, (k.rs = status.data(), k.i = (const uint32_t*)status.data() + 7), true);
+    WANT(t, k.a = (const vit_hip_dabplus_au*)nf.data(), true);
+    WANT(t, k.rows = 0, false);                                                          // no work
+    WANT(t, k.mf = 0, false);
+    WANT(t, (k.mf = 0, k.s = 25), true);                                                 // ... still refuses what needs no shape
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int shapes = argc > 1 ? atoi(argv[1]) : 300;
     rng_state = argc > 2 ? strtoull(argv[2], nullptr, 0) : 1;
+    if (arguments()) return 1;
     for (int it = 0; it < shapes; ++it)
         if (check_sync(it) || check_au(it)) return 1;
     printf("ok: %d shapes of each kernel, %llu access units checked\n", shapes, (unsigned long long)aus_checked);

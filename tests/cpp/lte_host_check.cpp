@@ -7,6 +7,8 @@
 // thread of the grid through the kernel's own lte_thread with the arguments lte_dematch_args makes, and compares the whole output with a
 // literal restatement of the rule -- the interleaver as a matrix with NULLs, the circular buffer walked entry by entry, a scalar loop
 // over k -- over a 0x5A fill.  The closed form of lte_position is also compared with that walk for every D in 1 .. 8192.
+// In front of them: the argument rule (lte_invalid) at an accepted call, at every INVALID_ARG case tests/test_gpu_lte_dematch.py sends
+// through the library, and at the zero-work case.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -139,9 +141,78 @@ static int one_shape(int it) {
     return 0;
 }
 
+// one call of the argument rule: the accepted base call, which a case changes in a field or two
+struct RuleCall {
+    bool handle = true;
+    int R = 3;
+    size_t sb = 2;
+    const void* rec;
+    size_t n = 4 * 40, stride = 40;
+    const uint32_t *off = nullptr, *count = nullptr;
+    size_t fr = 4, D = 10, E = 40;
+    unsigned shift = 0;
+    int lo = -32768, hi = 32767;
+    const void* out;
+    const char* operator()() const { return vit::lte_invalid(handle, R, sb, rec, n, stride, off, count, fr, D, E, shift, lo, hi, out); }
+};
+
+#define WANT(set, bad)                                                                      \
+    do {                                                                                    \
+        RuleCall k = base;                                                                  \
+        set;                                                                                \
+        const char* why_ = k();                                                             \
+        if ((why_ != nullptr) != (bad)) { printf("MISMATCH line %d: %s\n", __LINE__, why_ ? why_ : "accepted"); return 1; } \
+    } while (0)
+
+static int arguments() {
+    const size_t frames = 4, D = 10, E = 40;
+    std::vector<int16_t> in(frames * E + 3), outs(frames * 3 * D + 8);                  // heap blocks the rule never reads
+    std::vector<uint32_t> cnt(frames);
+    const uint8_t *a = (const uint8_t*)in.data(), *o = (const uint8_t*)outs.data();
+    RuleCall base;
+    base.rec = a; base.out = o;
+    WANT((void)0, false);
+    WANT(k.handle = false, true);
+    WANT(k.rec = nullptr, true);
+    WANT(k.out = nullptr, true);
+    WANT(k.R = 2, true);
+    WANT(k.D = 0, true);
+    WANT(k.D = 8193, true);
+    WANT(k.E = 0, true);
+    WANT(k.E = 1u << 24, true);
+    WANT(k.n = (size_t)1 << 32, true);
+    WANT(k.shift = 16, true);
+    WANT((k.lo = 5, k.hi = 4), true);
+    WANT(k.lo = -32769, true);
+    WANT(k.hi = 32768, true);
+    WANT((k.sb = 1, k.hi = 128), true);
+    WANT((k.sb = 1, k.lo = -129, k.hi = 0), true);
+    WANT(k.stride = E - 1, true);
+    WANT(k.n = frames * E - 1, true);
+    WANT(k.stride = E + 1, true);
+    WANT(k.out = a, true);                                                               // the output on the input
+    WANT(k.out = a + 2 * frames * E - 2, true);
+    WANT(k.out = (const void*)((uintptr_t)a - 2 * frames * 3 * D + 2), true);
+    WANT(k.out = (const void*)((uintptr_t)a - 2 * frames * 3 * D), false);               // right in front of it
+    WANT(k.rec = a + 1, true);                                                           // not aligned to soft16
+    WANT(k.out = o + 1, true);
+    WANT((k.sb = 1, k.lo = -128, k.hi = 127, k.rec = a + 1, k.out = o + 1), false);      // soft8: any address
+    WANT((k.off = cnt.data(), k.out = cnt.data()), true);
+    WANT((k.count = cnt.data(), k.out = cnt.data() + frames - 1), true);
+    WANT((k.fr = ((size_t)1 << 32) / 30 + 1, k.off = cnt.data()), true);
+    WANT((k.lo = 7, k.hi = 7), false);                                                   // the edges that pass
+    WANT((k.n = frames * E + 3, k.stride = E + 1), false);
+    WANT((k.E = (1u << 24) - 1, k.off = cnt.data()), false);
+    WANT(k.fr = 0, false);                                                               // no work
+    WANT((k.fr = 0, k.stride = 0), false);
+    WANT((k.fr = 0, k.shift = 16), true);                                                // ... still refuses what needs no shape
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int shapes = argc > 1 ? atoi(argv[1]) : 400;
     rng_state = argc > 2 ? strtoull(argv[2], nullptr, 0) : 1;
+    if (arguments()) return 1;
     // the closed form against the walk, every D
     for (uint32_t D = 1; D <= vit::LTE_MAX_D; ++D) {
         int16_t dummy = 0;

@@ -10,6 +10,8 @@
 // bit.  Rates, symbol counts, step counts and lengths include hostile values (above 7, 0xFFFFFFFF).  The one part of the DATA kernel that
 // stays off the host is the __shfl_xor exchange: the lanes of a group run one after the other and the partner's register comes from an
 // array.  The SIGNAL parser is run over all 2^18 fields.
+// In front of them: the three argument rules (wifi_deinterleave_invalid, wifi_signal_invalid, wifi_data_invalid) at an accepted call, at
+// every INVALID_ARG case tests/test_gpu_wifi.py sends through the library, and at the zero-work cases.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -253,9 +255,140 @@ static int data_shape(int it) {
     return 0;
 }
 
+// one call of an argument rule: the accepted base call, which a case changes in a field or two
+struct DeintCall {
+    bool handle = true;
+    int R = 2;
+    size_t sb = 2;
+    const void* src;
+    size_t stride = 0, frames = 4, max_sym = 1;
+    unsigned rate = 0;
+    const uint32_t *d_rate = nullptr, *d_n_sym = nullptr, *d_n_steps = nullptr;
+    size_t cs = 0, S = 216;
+    const void* dst;
+    const char* operator()() const {
+        return vit::wifi_deinterleave_invalid(handle, R, sb, src, stride, frames, max_sym, rate, d_rate, d_n_sym, d_n_steps, cs, S, dst);
+    }
+};
+struct SignalCall {
+    bool handle = true;
+    const uint8_t* src;
+    size_t stride = 0, frames = 4;
+    const vit_hip_wifi_signal* sig;
+    const char* operator()() const { return vit::wifi_signal_invalid(handle, src, stride, frames, sig); }
+};
+struct DataCall {
+    bool handle = true;
+    const uint8_t* src;
+    size_t stride = 0, frames = 4, S = 22 + 8 * 16;
+    const uint32_t* lengths;
+    size_t ls = 0, max_length = 16;
+    const uint8_t* dst;
+    size_t ps = 0;
+    const vit_hip_wifi_status* st;
+    const char* operator()() const { return vit::wifi_data_invalid(handle, src, stride, frames, S, lengths, ls, max_length, dst, ps, st); }
+};
+
+#define WANT(base, set, bad)                                                                \
+    do {                                                                                    \
+        auto k = base;                                                                      \
+        set;                                                                                \
+        const char* why_ = k();                                                             \
+        if ((why_ != nullptr) != (bad)) { printf("MISMATCH line %d: %s\n", __LINE__, why_ ? why_ : "accepted"); return 1; } \
+    } while (0)
+
+static int arguments() {
+    std::vector<int16_t> d_in(4 * 288), out(4 * 216 * 2 + 8);                           // heap blocks the rules never read
+    std::vector<uint32_t> counts(8);
+    auto plus = [](const void* p, size_t bytes) { return (const void*)((const uint8_t*)p + bytes); };
+    DeintCall g;
+    g.src = d_in.data(); g.dst = out.data();
+    WANT(g, (void)0, false);
+    WANT(g, k.handle = false, true);
+    WANT(g, k.src = nullptr, true);
+    WANT(g, k.dst = nullptr, true);
+    WANT(g, k.R = 3, true);
+    WANT(g, k.rate = 8, true);
+    WANT(g, (k.rate = 8, k.d_rate = counts.data()), false);                             // with d_rate the scalar is not looked at
+    WANT(g, k.max_sym = 0, true);
+    WANT(g, k.S = 0, true);
+    WANT(g, k.stride = 47, true);                                                        // strides
+    WANT(g, k.stride = 48, false);
+    WANT(g, (k.d_rate = counts.data(), k.stride = 287), true);
+    WANT(g, (k.d_rate = counts.data(), k.stride = 288), false);
+    WANT(g, k.dst = plus(out.data(), 2), true);                                          // alignment
+    WANT(g, k.src = plus(d_in.data(), 1), true);
+    WANT(g, (k.sb = 1, k.src = plus(d_in.data(), 1)), false);
+    WANT(g, k.d_n_sym = (const uint32_t*)plus(counts.data(), 2), true);
+    WANT(g, k.dst = d_in.data(), true);                                                  // overlaps
+    WANT(g, k.dst = d_in.data() + 4 * 288 - 2, true);
+    WANT(g, k.dst = d_in.data() + 4 * 288, false);
+    WANT(g, k.d_rate = (const uint32_t*)out.data(), true);
+    WANT(g, k.d_n_steps = (const uint32_t*)out.data() + 4 * 216 - 1, true);
+    WANT(g, k.d_n_steps = (const uint32_t*)out.data() + 4 * 216, false);
+    WANT(g, (k.d_n_steps = (const uint32_t*)out.data() - 4, k.cs = 2), true);            // entries two apart reach further
+    WANT(g, k.d_n_steps = (const uint32_t*)out.data() - 4, false);
+    WANT(g, k.max_sym = ((size_t)1 << 32) / 288 + 1, true);                              // counts
+    WANT(g, k.S = ((size_t)1 << 31) - 1, true);
+    WANT(g, (k.frames = (size_t)1 << 33, k.S = 1), true);
+    WANT(g, k.cs = (size_t)1 << 32, true);
+    WANT(g, (k.frames = 0, k.max_sym = 0, k.S = 0), false);                              // no work
+    WANT(g, (k.frames = 0, k.R = 3), true);                                              // ... still refuses what needs no shape
+
+    std::vector<uint8_t> b(4 * 40), psdu(4 * 16);
+    std::vector<vit_hip_wifi_signal> sig(5);
+    SignalCall q;
+    q.src = b.data(); q.sig = sig.data();
+    WANT(q, (void)0, false);
+    WANT(q, k.handle = false, true);
+    WANT(q, k.src = nullptr, true);
+    WANT(q, k.sig = nullptr, true);
+    WANT(q, k.stride = 2, true);
+    WANT(q, k.stride = 3, false);
+    WANT(q, k.sig = (const vit_hip_wifi_signal*)plus(sig.data(), 2), true);
+    WANT(q, k.src = (const uint8_t*)sig.data(), true);
+    WANT(q, k.src = (const uint8_t*)sig.data() + 4 * sizeof(vit_hip_wifi_signal) - 1, true);
+    WANT(q, k.src = (const uint8_t*)sig.data() + 4 * sizeof(vit_hip_wifi_signal), false);
+    WANT(q, k.frames = (size_t)0x7FFFFFFFu * 256 + 1, true);
+    WANT(q, k.frames = 0, false);                                                        // no work
+    WANT(q, (k.frames = 0, k.stride = 2), true);
+
+    std::vector<vit_hip_wifi_status> status(4);
+    DataCall d;
+    d.src = b.data(); d.lengths = counts.data(); d.dst = psdu.data(); d.st = status.data();
+    WANT(d, (void)0, false);
+    WANT(d, k.handle = false, true);
+    WANT(d, k.src = nullptr, true);
+    WANT(d, k.lengths = nullptr, true);
+    WANT(d, k.dst = nullptr, true);
+    WANT(d, k.st = nullptr, true);
+    WANT(d, k.S = 21, true);
+    WANT(d, k.S = ((size_t)1 << 31) - 1, true);
+    WANT(d, k.stride = 17, true);                                                        // strides
+    WANT(d, k.stride = 18, false);
+    WANT(d, k.ps = 15, true);
+    WANT(d, k.ps = 16, false);
+    WANT(d, k.st = (const vit_hip_wifi_status*)plus(status.data(), 2), true);            // alignment
+    WANT(d, k.lengths = (const uint32_t*)plus(counts.data(), 1), true);
+    WANT(d, k.dst = b.data(), true);                                                     // overlaps
+    WANT(d, k.dst = b.data() + 3 * 18 + 17, true);
+    WANT(d, k.dst = b.data() + 3 * 18 + 18, false);
+    WANT(d, k.st = (const vit_hip_wifi_status*)counts.data(), true);
+    WANT(d, k.dst = (const uint8_t*)(counts.data() + 3), true);
+    WANT(d, k.dst = (const uint8_t*)(counts.data() + 4), false);
+    WANT(d, (k.dst = (const uint8_t*)(counts.data() + 4), k.ls = 2), true);              // lengths two apart reach further
+    WANT(d, k.dst = (const uint8_t*)status.data() + 4 * sizeof(vit_hip_wifi_status) - 1, true);
+    WANT(d, k.max_length = (size_t)1 << 28, true);
+    WANT(d, k.ls = (size_t)1 << 32, true);
+    WANT(d, k.frames = 0, false);                                                        // no work
+    WANT(d, (k.frames = 0, k.S = 21), true);                                             // ... still refuses what needs no shape
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int shapes = argc > 1 ? atoi(argv[1]) : 300;
     rng_state = argc > 2 ? strtoull(argv[2], nullptr, 0) : 1;
+    if (arguments()) return 1;
     // the closed form of the place against the table, and the checks of the permutation
     for (uint32_t m = 0; m < 8; ++m) {
         const std::vector<uint32_t> table = rule_table(m);

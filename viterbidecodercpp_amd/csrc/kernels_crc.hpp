@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "../../include/vit_hip.h"
+#include "arg_rules.hpp"
 
 namespace vit {
 
@@ -197,6 +198,30 @@ __global__ void __launch_bounds__(CRC_BLOCK) crc_batch_kernel(CrcArgs a) {
     uint32_t reg = L.active ? crc_chunk(a, tab, L.base, L.j) : 0u;
     for (uint32_t s = 0; s < a.logG; ++s) reg = crc_combine(a, reg, __shfl_xor(reg, 1 << s), s);
     if (L.active && L.j == 0) crc_finish(a, L, reg);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------------
+
+// argument rule (include/vit_hip.h): everything the host can know without reading device memory
+inline const char* crc_invalid(bool handle, const vit_hip_crc_params* c, const uint8_t* d_frames, size_t stride, size_t rows, size_t max_frames,
+                               size_t first_bit, size_t n_bits, const uint32_t* d_crc, const uint32_t* d_syndrome) {
+    if (!handle || !c || !d_frames) return "NULL handle, crc or d_frames";
+    if (!d_crc && !d_syndrome) return "d_crc and d_syndrome are both NULL";
+    if (c->width < 1 || c->width > 32) return "width must be 1 .. 32";
+    const uint64_t top = 1ull << c->width;
+    if (c->poly >= top || c->init >= top || c->xorout >= top) return "poly, init and xorout must lie below 2^width";
+    if (first_bit >= 0xFFFFFFFFull || n_bits >= 0xFFFFFFFFull || first_bit + n_bits + 32 >= 0xFFFFFFFFull)
+        return "first_bit + n_bits + 32 must lie below 2^32 - 1";
+    const size_t need = (first_bit + n_bits + (d_syndrome ? c->width : 0u) + 7) / 8;
+    if (stride != 0 && stride < need) return "frame_stride_bytes does not cover first_bit + n_bits (+ width)";
+    if (rows == 0 || max_frames == 0) return nullptr;
+    if (rows > 0x7FFFFFFFu || max_frames > 0x7FFFFFFFu) return "more than 2^31 - 1 blocks";
+    const size_t frames = rows * max_frames;
+    if (frames > ((uint64_t)0x7FFFFFFFu * CRC_BLOCK) >> crc_geometry(n_bits).logG) return "more than 2^31 - 1 blocks";
+    const size_t in_b = extent(frames, stride ? stride : need, need), out_b = frames * sizeof(uint32_t);
+    if (overlap(d_crc, out_b, d_syndrome, out_b)) return "d_crc overlaps d_syndrome";
+    if (overlap(d_crc, out_b, d_frames, in_b) || overlap(d_syndrome, out_b, d_frames, in_b)) return "an output overlaps d_frames";
+    return nullptr;
 }
 
 // the kernel arguments of a call the argument rule has accepted (rows, max_frames >= 1); poly, init, xorout below 2^width

@@ -31,6 +31,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "arg_rules.hpp"
+
 namespace vit {
 
 constexpr uint32_t DVBT_BLOCK = 256;
@@ -185,11 +187,6 @@ __global__ void __launch_bounds__(DVBT_BLOCK) dvbt_deinterleave_kernel(DvbtArgs 
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
 
-inline bool dvbt_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 // argument rules (include/vit_hip.h): everything the host can know without reading device memory.  R and soft_bytes are the handle's
 inline const char* dvbt_invalid(bool handle, int R, size_t sb, const void* d_in, size_t in_row_stride, size_t rows, size_t n_sym, unsigned mode,
                                 unsigned v, unsigned rate, const uint32_t* d_parity_in, const uint32_t* d_parity_out, const void* d_out,
@@ -199,8 +196,8 @@ inline const char* dvbt_invalid(bool handle, int R, size_t sb, const void* d_in,
     if (mode >= DVBT_MODES) return "mode must be 0 (2k), 1 (4k) or 2 (8k)";
     if (v != 2 && v != 4 && v != 6) return "v must be 2, 4 or 6";
     if (rate >= DVBT_RATES) return "rate must be 0 .. 4";
-    if ((uintptr_t)d_in % sb || (uintptr_t)d_out % 4) return "d_in must be aligned to the symbol type, d_symbols_out to 4 bytes";
-    if ((uintptr_t)d_parity_in % 4 || (uintptr_t)d_parity_out % 4) return "d_parity_in and d_parity_out must be aligned to 4 bytes";
+    if (misaligned(d_in, sb) || misaligned(d_out, 4)) return "d_in must be aligned to the symbol type, d_symbols_out to 4 bytes";
+    if (misaligned(d_parity_in, 4) || misaligned(d_parity_out, 4)) return "d_parity_in and d_parity_out must be aligned to 4 bytes";
     if (rows == 0 || n_sym == 0) return nullptr;
     const uint64_t sym_in = (uint64_t)dvbt_nmax(mode) * v, sps = dvbt_steps_per_symbol(mode, v, rate);
     if (n_sym > 0xFFFFFFFFull / sym_in) return "n_sym * Nmax * v must lie below 2^32";
@@ -211,14 +208,14 @@ inline const char* dvbt_invalid(bool handle, int R, size_t sb, const void* d_in,
     const uint64_t is = in_row_stride ? in_row_stride : row_in, os = out_row_stride ? out_row_stride : row_steps;
     if (is > 0xFFFFFFFFull || os > 0xFFFFFFFFull) return "the row strides must lie below 2^32";
     if (sb == 1 && rows > 1 && (os & 1u)) return "out_row_stride must be even at 8-bit symbols: every row starts a dword";
-    const uint64_t in_el = (rows - 1) * is + row_in, out_el = 2 * ((rows - 1) * os + row_steps);
+    const uint64_t in_el = extent(rows, is, row_in), out_el = 2 * extent(rows, os, row_steps);
     if (in_el * sb >= 4 * 0x100000000ull || out_el * sb >= 4 * 0x100000000ull) return "input and output must each fill fewer than 2^32 dwords";
     if (rows * n_sym * (dvbt_nmax(mode) / DVBT_UNIT) > 0x7FFFFFF8ull) return "more than 2^31 - 8 blocks";
     const uint64_t in_b = in_el * sb, out_b = out_el * sb, par_b = rows * 4;
-    if (dvbt_overlap(d_out, out_b, d_in, in_b)) return "d_symbols_out overlaps d_in";
-    if (dvbt_overlap(d_out, out_b, d_parity_in, par_b) || dvbt_overlap(d_out, out_b, d_parity_out, par_b))
+    if (overlap(d_out, out_b, d_in, in_b)) return "d_symbols_out overlaps d_in";
+    if (overlap(d_out, out_b, d_parity_in, par_b) || overlap(d_out, out_b, d_parity_out, par_b))
         return "d_symbols_out overlaps d_parity_in or d_parity_out";
-    if (dvbt_overlap(d_parity_out, par_b, d_in, in_b) || dvbt_overlap(d_parity_out, par_b, d_parity_in, par_b))
+    if (overlap(d_parity_out, par_b, d_in, in_b) || overlap(d_parity_out, par_b, d_parity_in, par_b))
         return "d_parity_out overlaps d_in or d_parity_in";
     return nullptr;
 }

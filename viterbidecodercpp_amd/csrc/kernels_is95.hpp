@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/vit_hip.h"
+#include "arg_rules.hpp"
 
 namespace vit {
 
@@ -195,11 +196,6 @@ __global__ void __launch_bounds__(IS95_BLOCK) is95_zero_kernel(Is95ZeroArgs a) {
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
 
-inline bool is95_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 // argument rules (include/vit_hip.h): everything the host can know without reading device memory.  R and sb are the handle's
 inline const char* is95_deinterleave_invalid(bool handle, int R, size_t sb, const void* d_in, size_t in_frame_stride, size_t frames,
                                              const uint8_t* d_scramble, size_t scramble_frame_stride, unsigned shift, int lo, int hi,
@@ -210,22 +206,22 @@ inline const char* is95_deinterleave_invalid(bool handle, int R, size_t sb, cons
     if (shift > 15) return "shift must be 0 .. 15";
     const int top = sb == 2 ? 32767 : 127;
     if (lo > hi || lo < -top - 1 || hi > top) return "clamp_lo .. clamp_hi must be a range of the symbol type";
-    if ((uintptr_t)d_in % sb) return "d_in must be aligned to the symbol type";
+    if (misaligned(d_in, sb)) return "d_in must be aligned to the symbol type";
     for (int h = 0; h < 4; ++h)
-        if ((uintptr_t)d_out[h] % 4) return "every output must be aligned to 4 bytes";
+        if (misaligned(d_out[h], 4)) return "every output must be aligned to 4 bytes";
     if (in_frame_stride != 0 && in_frame_stride < IS95_SYMBOLS) return "in_frame_stride below 384";
     if (d_scramble && scramble_frame_stride != 0 && scramble_frame_stride < IS95_MASK_BYTES) return "scramble_frame_stride below 48";
     if (in_frame_stride >= 0x7FFFFFFFull || scramble_frame_stride >= 0x7FFFFFFFull) return "the strides must lie below 2^31 - 1";
     if (frames >= 0x7FFFFFFFull) return "frames must lie below 2^31 - 1";
     if (frames == 0) return nullptr;
     const uint64_t is = in_frame_stride ? in_frame_stride : IS95_SYMBOLS;
-    const uint64_t in_b = ((frames - 1) * is + IS95_SYMBOLS) * sb, mask_b = (frames - 1) * (uint64_t)scramble_frame_stride + IS95_MASK_BYTES;
+    const uint64_t in_b = extent(frames, is, IS95_SYMBOLS) * sb, mask_b = extent(frames, scramble_frame_stride, IS95_MASK_BYTES);
     for (int h = 0; h < 4; ++h) {
         const uint64_t out_b = frames * 2 * is95_steps(h) * sb;
-        if (is95_overlap(d_out[h], out_b, d_in, in_b)) return "an output overlaps d_in";
-        if (is95_overlap(d_out[h], out_b, d_scramble, mask_b)) return "an output overlaps d_scramble";
+        if (overlap(d_out[h], out_b, d_in, in_b)) return "an output overlaps d_in";
+        if (overlap(d_out[h], out_b, d_scramble, mask_b)) return "an output overlaps d_scramble";
         for (int g = h + 1; g < 4; ++g)
-            if (is95_overlap(d_out[h], out_b, d_out[g], frames * 2 * is95_steps(g) * sb)) return "two outputs overlap";
+            if (overlap(d_out[h], out_b, d_out[g], frames * 2 * is95_steps(g) * sb)) return "two outputs overlap";
     }
     return nullptr;
 }
@@ -254,11 +250,11 @@ inline const char* is95_decide_invalid(bool handle, const uint8_t* const* d_byte
     if (ser_den == 0) return "ser_den must be at least 1";
     if (info_stride != 0 && info_stride < IS95_INFO_BYTES) return "info_stride below 22";
     if (info_stride >= 0x7FFFFFFFull) return "the strides must lie below 2^31 - 1";
-    if ((uintptr_t)d_decision % 4) return "d_decision must be aligned to 4 bytes";
+    if (misaligned(d_decision, 4)) return "d_decision must be aligned to 4 bytes";
     for (int h = 0; h < 4; ++h) {
         if (!d_bytes[h]) continue;
         if (!d_errors[h] || !d_compared[h] || (h < 2 && !d_syndrome[h])) return "a present hypothesis needs d_errors, d_compared and, at h < 2, d_syndrome";
-        if ((uintptr_t)d_errors[h] % 4 || (uintptr_t)d_compared[h] % 4 || (h < 2 && (uintptr_t)d_syndrome[h] % 4))
+        if (misaligned(d_errors[h], 4) || misaligned(d_compared[h], 4) || (h < 2 && misaligned(d_syndrome[h], 4)))
             return "the count arrays must be aligned to 4 bytes";
         if (bytes_stride && bytes_stride[h] != 0 && bytes_stride[h] < is95_bytes(h)) return "a bytes stride below 23, 11, 5 or 2";
         if (bytes_stride && bytes_stride[h] >= 0x7FFFFFFFull) return "the strides must lie below 2^31 - 1";
@@ -266,16 +262,16 @@ inline const char* is95_decide_invalid(bool handle, const uint8_t* const* d_byte
     if (frames >= 0x7FFFFFFFull) return "frames must lie below 2^31 - 1";
     if (frames == 0) return nullptr;
     const uint64_t dec_b = frames * sizeof(vit_hip_is95_decision);
-    const uint64_t info_b = (frames - 1) * (uint64_t)(info_stride ? info_stride : IS95_INFO_BYTES) + IS95_INFO_BYTES, cnt_b = frames * 4;
-    if (is95_overlap(d_decision, dec_b, d_info, info_b)) return "d_decision overlaps d_info";
+    const uint64_t info_b = extent(frames, info_stride ? info_stride : IS95_INFO_BYTES, IS95_INFO_BYTES), cnt_b = frames * 4;
+    if (overlap(d_decision, dec_b, d_info, info_b)) return "d_decision overlaps d_info";
     for (int h = 0; h < 4; ++h) {
         if (!d_bytes[h]) continue;
-        const uint64_t bs = bytes_stride && bytes_stride[h] ? bytes_stride[h] : is95_bytes(h), in_b = (frames - 1) * bs + is95_bytes(h);
+        const uint64_t bs = bytes_stride && bytes_stride[h] ? bytes_stride[h] : is95_bytes(h), in_b = extent(frames, bs, is95_bytes(h));
         const void* outs[2] = {d_decision, d_info};
         const uint64_t out_b[2] = {dec_b, info_b};
         for (int o = 0; o < 2; ++o)
-            if (is95_overlap(outs[o], out_b[o], d_bytes[h], in_b) || is95_overlap(outs[o], out_b[o], d_errors[h], cnt_b) ||
-                is95_overlap(outs[o], out_b[o], d_compared[h], cnt_b) || (h < 2 && is95_overlap(outs[o], out_b[o], d_syndrome[h], cnt_b)))
+            if (overlap(outs[o], out_b[o], d_bytes[h], in_b) || overlap(outs[o], out_b[o], d_errors[h], cnt_b) ||
+                overlap(outs[o], out_b[o], d_compared[h], cnt_b) || (h < 2 && overlap(outs[o], out_b[o], d_syndrome[h], cnt_b)))
                 return "an output overlaps an input";
     }
     return nullptr;
@@ -308,7 +304,7 @@ inline const char* is95_errors_invalid(bool handle, int K, int R, size_t sb, con
     for (int h = 0; h < 4; ++h) {
         if (!d_bytes[h]) continue;
         if (!d_symbols[h] || !d_errors[h] || !d_compared[h]) return "a present hypothesis needs d_symbols, d_errors and d_compared";
-        if ((uintptr_t)d_symbols[h] % sb || (uintptr_t)d_errors[h] % 4 || (uintptr_t)d_compared[h] % 4)
+        if (misaligned(d_symbols[h], sb) || misaligned(d_errors[h], 4) || misaligned(d_compared[h], 4))
             return "d_symbols must be aligned to the symbol type, the count arrays to 4 bytes";
         if (bytes_stride && bytes_stride[h] != 0 && bytes_stride[h] < is95_bytes(h)) return "a bytes stride below 23, 11, 5 or 2";
         if (bytes_stride && bytes_stride[h] >= 0x7FFFFFFFull) return "the strides must lie below 2^31 - 1";
@@ -319,15 +315,15 @@ inline const char* is95_errors_invalid(bool handle, int K, int R, size_t sb, con
     for (int h = 0; h < 4; ++h) {
         if (!d_bytes[h]) continue;
         const void* outs[2] = {d_errors[h], d_compared[h]};
-        if (is95_overlap(outs[0], cnt_b, outs[1], cnt_b)) return "two count arrays overlap";
+        if (overlap(outs[0], cnt_b, outs[1], cnt_b)) return "two count arrays overlap";
         for (int g = 0; g < 4; ++g) {
             if (!d_bytes[g]) continue;
             const uint64_t gs = bytes_stride && bytes_stride[g] ? bytes_stride[g] : is95_bytes(g);
             for (int o = 0; o < 2; ++o) {
-                if (g != h && (is95_overlap(outs[o], cnt_b, d_errors[g], cnt_b) || is95_overlap(outs[o], cnt_b, d_compared[g], cnt_b)))
+                if (g != h && (overlap(outs[o], cnt_b, d_errors[g], cnt_b) || overlap(outs[o], cnt_b, d_compared[g], cnt_b)))
                     return "two count arrays overlap";
-                if (is95_overlap(outs[o], cnt_b, d_bytes[g], (frames - 1) * gs + is95_bytes(g)) ||
-                    is95_overlap(outs[o], cnt_b, d_symbols[g], frames * 2 * is95_steps(g) * sb))
+                if (overlap(outs[o], cnt_b, d_bytes[g], extent(frames, gs, is95_bytes(g))) ||
+                    overlap(outs[o], cnt_b, d_symbols[g], frames * 2 * is95_steps(g) * sb))
                     return "a count array overlaps an input";
             }
         }

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/vit_hip.h"
+#include "arg_rules.hpp"
 
 namespace vit {
 
@@ -133,6 +134,31 @@ __device__ inline void lte_thread(const LteArgs& a, uint32_t block, uint32_t tid
 template <class soft_t>
 __global__ void __launch_bounds__(LTE_BLOCK) lte_dematch_kernel(LteArgs a) {
     lte_thread<soft_t>(a, blockIdx.x, threadIdx.x);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------------
+
+// argument rule (include/vit_hip.h): everything the host can know without reading device memory.  R and sb are the handle's
+inline const char* lte_invalid(bool handle, int R, size_t sb, const void* d_received, size_t n_received, size_t stride, const uint32_t* d_offset,
+                               const uint32_t* d_count, size_t frames, size_t D, size_t E_max, unsigned shift, int lo, int hi, const void* d_out) {
+    if (!handle || !d_received || !d_out) return "NULL handle, d_received or d_symbols_out";
+    if (R != 3) return "the handle's code rate must be 1/3";
+    if (D == 0 || D > LTE_MAX_D) return "D must be 1 .. 8192";
+    if (E_max == 0 || E_max >= (1u << 24)) return "E_max must be 1 .. 2^24 - 1";
+    if (n_received >= 0x100000000ull) return "n_received must lie below 2^32";
+    if (shift > 15) return "shift must be 0 .. 15";
+    const int top = sb == 2 ? 32767 : 127;
+    if (lo > hi || lo < -top - 1 || hi > top) return "clamp_lo .. clamp_hi must be a range of the symbol type";
+    if (misaligned(d_received, sb) || misaligned(d_out, sb)) return "d_received and d_symbols_out must be aligned to the symbol type";
+    if (frames == 0) return nullptr;
+    if (!d_offset && (stride < E_max || n_received < E_max || (frames - 1) > (n_received - E_max) / stride))
+        return "received_frame_stride below E_max, or (frames - 1) * stride + E_max above n_received";
+    if (frames > 0xFFFFFFFFull / (3 * D)) return "frames * 3 D must lie below 2^32";
+    const size_t out_b = frames * 3 * D * sb;
+    if (overlap(d_out, out_b, d_received, n_received * sb)) return "d_symbols_out overlaps d_received";
+    if (overlap(d_out, out_b, d_offset, frames * sizeof(uint32_t)) || overlap(d_out, out_b, d_count, frames * sizeof(uint32_t)))
+        return "d_symbols_out overlaps d_offset or d_count";
+    return nullptr;
 }
 
 // the kernel arguments of a call the argument rule has accepted: frames >= 1, frames * 3 D < 2^32, pointers aligned to soft_t

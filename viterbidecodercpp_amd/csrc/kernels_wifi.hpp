@@ -407,6 +407,68 @@ inline WifiDataArgs wifi_data_args(const uint8_t* d_bytes, size_t stride, size_t
 
 inline uint64_t wifi_data_blocks(const WifiDataArgs& a) { return ((a.frames << a.logG) + WIFI_BLOCK - 1) / WIFI_BLOCK; }
 
+// ---- host side -----------------------------------------------------------------------------------------------------------------------------
+
+// argument rules (include/vit_hip.h): everything the host can know without reading device memory.  R and sb are the handle's
+inline const char* wifi_deinterleave_invalid(bool handle, int R, size_t sb, const void* d_in, size_t stride, size_t frames, size_t max_sym,
+                                             unsigned rate, const uint32_t* d_rate, const uint32_t* d_n_sym, const uint32_t* d_n_steps,
+                                             size_t count_stride, size_t S, const void* d_out) {
+    if (!handle || !d_in || !d_out) return "NULL handle, d_in or d_symbols_out";
+    if (R != 2) return "the handle's code rate must be 1/2";
+    if (!d_rate && rate > 7) return "rate must be 0 .. 7";
+    if (misaligned(d_in, sb) || misaligned(d_out, 4)) return "d_in must be aligned to the symbol type, d_symbols_out to 4 bytes";
+    if (misaligned(d_rate, 4) || misaligned(d_n_sym, 4) || misaligned(d_n_steps, 4)) return "d_rate, d_n_sym and d_n_steps must be aligned to 4 bytes";
+    if (frames == 0) return nullptr;
+    if (max_sym == 0 || S == 0) return "max_sym and S must be at least 1";
+    if (max_sym > 0xFFFFFFFFull / WIFI_MAX_CBPS) return "max_sym * 288 must lie below 2^32";
+    if (S >= 0x7FFFFFFFull) return "S must lie below 2^31 - 1";
+    const size_t least = max_sym * (d_rate ? WIFI_MAX_CBPS : wifi_rate(rate).ncbps);
+    if (stride != 0 && stride < least) return "in_frame_stride below max_sym * N_CBPS (288 with d_rate)";
+    if (frames > (0xFFFFFFFFull * (4 / sb)) / (2 * S)) return "frames * 2 S symbols must fill fewer than 2^32 dwords";
+    if (count_stride > 0xFFFFFFFFull || frames > 0xFFFFFFFFull) return "frames and count_stride must lie below 2^32";
+    const size_t in_stride = stride ? stride : max_sym * WIFI_MAX_CBPS;
+    const size_t out_b = frames * 2 * S * sb, in_b = extent(frames, in_stride, stride ? least : in_stride) * sb;
+    const size_t cnt_b = extent(frames, count_stride ? count_stride : 1, 1) * sizeof(uint32_t);
+    if (overlap(d_out, out_b, d_in, in_b)) return "d_symbols_out overlaps d_in";
+    if (overlap(d_out, out_b, d_rate, cnt_b) || overlap(d_out, out_b, d_n_sym, cnt_b) || overlap(d_out, out_b, d_n_steps, cnt_b))
+        return "d_symbols_out overlaps d_rate, d_n_sym or d_n_steps";
+    return nullptr;
+}
+
+inline const char* wifi_signal_invalid(bool handle, const uint8_t* d_bytes, size_t stride, size_t frames, const vit_hip_wifi_signal* d_signal) {
+    if (!handle || !d_bytes || !d_signal) return "NULL handle, d_bytes or d_signal";
+    if (stride != 0 && stride < 3) return "frame_stride_bytes below 3";
+    if (misaligned(d_signal, 4)) return "d_signal must be aligned to 4 bytes";
+    if (frames == 0) return nullptr;
+    if (frames > (uint64_t)0x7FFFFFFFu * WIFI_BLOCK) return "more than 2^31 - 1 blocks";
+    if (overlap(d_signal, frames * sizeof(vit_hip_wifi_signal), d_bytes, extent(frames, stride ? stride : 3, 3))) return "d_signal overlaps d_bytes";
+    return nullptr;
+}
+
+inline const char* wifi_data_invalid(bool handle, const uint8_t* d_bytes, size_t stride, size_t frames, size_t S, const uint32_t* d_length,
+                                     size_t length_stride, size_t max_length, const uint8_t* d_psdu, size_t psdu_stride,
+                                     const vit_hip_wifi_status* d_status) {
+    if (!handle || !d_bytes || !d_length || !d_psdu || !d_status) return "NULL handle, d_bytes, d_length, d_psdu or d_status";
+    if (S < 22 || S >= 0x7FFFFFFFull) return "S must be 22 .. 2^31 - 2: the SERVICE field and the tail";
+    if (max_length > 0x0FFFFFFFull) return "max_length must lie below 2^28";
+    const size_t n_bits = S - 6, nb = (n_bits + 7) / 8;
+    if (stride != 0 && stride < nb) return "frame_stride_bytes below ceil((S - 6) / 8)";
+    const size_t room = (n_bits - 16) / 8, longest = max_length < room ? max_length : room;
+    if (psdu_stride != 0 && psdu_stride < longest) return "psdu_stride below the longest PSDU the call can write";
+    if (misaligned(d_length, 4) || misaligned(d_status, 4)) return "d_length and d_status must be aligned to 4 bytes";
+    if (frames == 0) return nullptr;
+    if (length_stride > 0xFFFFFFFFull) return "length_stride must lie below 2^32";
+    const uint32_t logG = crc_geometry(longest > 4 ? 8ull * (longest - 4) : 0ull).logG;
+    if (frames > ((uint64_t)0x7FFFFFFFu * WIFI_BLOCK) >> logG) return "more than 2^31 - 1 blocks";
+    const size_t in_b = extent(frames, stride ? stride : nb, nb), len_b = extent(frames, length_stride ? length_stride : 1, 1) * sizeof(uint32_t);
+    const size_t psdu_b = longest ? extent(frames, psdu_stride ? psdu_stride : max_length, longest) : 0;
+    const size_t st_b = frames * sizeof(vit_hip_wifi_status);
+    if (overlap(d_psdu, psdu_b, d_bytes, in_b) || overlap(d_status, st_b, d_bytes, in_b)) return "an output overlaps d_bytes";
+    if (overlap(d_psdu, psdu_b, d_length, len_b) || overlap(d_status, st_b, d_length, len_b)) return "an output overlaps d_length";
+    if (overlap(d_psdu, psdu_b, d_status, st_b)) return "d_psdu overlaps d_status";
+    return nullptr;
+}
+
 // ---- launchers (hipGetLastError() after each: 0 / -1) --------------------------------------------------------------------------------
 
 inline int wifi_launch_deinterleave(const WifiDeintArgs& a, size_t soft_bytes, hipStream_t st) {

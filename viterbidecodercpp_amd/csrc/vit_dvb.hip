@@ -10,14 +10,6 @@ using namespace vit;
 
 namespace {
 
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
-// bytes from the first packet's first byte to the last packet's last
-size_t extent(size_t packets, size_t stride, size_t bytes) { return packets ? (packets - 1) * stride + bytes : 0; }
-
 // argument rule (include/vit_hip.h): everything the host can know without reading device memory.  *H_out: packets of history
 const char* deinterleave_invalid(vit_hip_handle h, const uint8_t* d_in, size_t stride, size_t rows, size_t max_frames, const uint32_t* d_n_frames,
                                  size_t B, size_t M, size_t n, const uint8_t* d_hist_in, const uint32_t* d_fill_in, size_t hist_stride,

@@ -29,7 +29,7 @@ int enc_prepare(vit_hip_handle h, const void* d_symbols, size_t symbol_frame_str
     const size_t nbytes = (L + 7) / 8;
     if (symbol_frame_stride != 0 && symbol_frame_stride < steps * R) return fail(VIT_HIP_ERR_INVALID_ARG, "symbol_frame_stride is below steps * R");
     if (bytes_frame_stride != 0 && bytes_frame_stride < nbytes) return fail(VIT_HIP_ERR_INVALID_ARG, "bytes_frame_stride is below ceil(L/8)");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    if (h->soft_bytes == 2 && misaligned(d_symbols, 2)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
     if (R > 8) return fail(VIT_HIP_ERR_UNSUPPORTED, "R > 8");
     const size_t nchunks = (steps + 7) / 8;
     if (frames > 0xFFFFFFFFull || frames > 0xFFFFFFFFFFFFFFFFull / nchunks) return fail(VIT_HIP_ERR_INVALID_ARG, "batch too large for one launch");

@@ -27,11 +27,6 @@ __global__ void reset_kernel(error_t* met, const uint32_t* start, size_t frames,
 }  // namespace vit
 
 namespace {
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;                 // differences, not sums: an extent may reach the end of memory
-    return a_bytes && b_bytes && (x >= y ? x - y < b_bytes : y - x < a_bytes);
-}
-
 int lds_waves(int N) {
     if (N <= 256) return 1;
     int w = N / 256;
@@ -421,8 +416,8 @@ int vit::update_batch_impl(vit_hip_handle h, const void* d_symbols, size_t sym_s
     // the windows of one stream overlap (vit_hip_decode_stream: the kernels only read the symbols); every other caller's chunks do not
     if (sym_stride < n_steps * (size_t)h->R && !overlapped_chunks) return fail(VIT_HIP_ERR_INVALID_ARG, "symbol_frame_stride shorter than one chunk");
     if (workspace_bytes < vit_hip_workspace_bytes(h, frames, L)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    if (misaligned(d_workspace, 256)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (h->soft_bytes == 2 && misaligned(d_symbols, 2)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
     if (n_steps == 0) return VIT_HIP_OK;
     VIT_HIP_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
@@ -527,14 +522,14 @@ int vit_hip_depuncture_batch(vit_hip_handle h, const void* d_punctured, size_t p
     const size_t chunks = (symbols_per_frame + 7) / 8;
     if (frames > 0x7FFFFFFFull * 256ull / chunks) return fail(VIT_HIP_ERR_INVALID_ARG, "batch too large for one launch");
     const size_t sb = (size_t)h->soft_bytes;
-    if ((uintptr_t)d_punctured % sb || (uintptr_t)d_symbols_out % sb)
+    if (misaligned(d_punctured, sb) || misaligned(d_symbols_out, sb))
         return fail(VIT_HIP_ERR_INVALID_ARG, "d_punctured and d_symbols_out must be aligned to the symbol type");
-    if ((uintptr_t)d_source_index % sizeof(int32_t)) return fail(VIT_HIP_ERR_INVALID_ARG, "d_source_index must be aligned to 4 bytes");
+    if (misaligned(d_source_index, sizeof(int32_t))) return fail(VIT_HIP_ERR_INVALID_ARG, "d_source_index must be aligned to 4 bytes");
     // the extents the kernel can touch (the map is bounded by punctured_per_frame on the device); an input too large to state is "all of memory"
     const size_t out_b = frames * symbols_per_frame * sb;
     const size_t in_b = punctured_per_frame > (size_t)-1 / sb / frames ? (size_t)-1 - (uintptr_t)d_punctured : frames * punctured_per_frame * sb;
-    if (ranges_overlap(d_symbols_out, out_b, d_punctured, in_b)) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols_out overlaps d_punctured");
-    if (ranges_overlap(d_symbols_out, out_b, d_source_index, symbols_per_frame * sizeof(int32_t)))
+    if (overlap(d_symbols_out, out_b, d_punctured, in_b)) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols_out overlaps d_punctured");
+    if (overlap(d_symbols_out, out_b, d_source_index, symbols_per_frame * sizeof(int32_t)))
         return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols_out overlaps d_source_index");
     VIT_HIP_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;

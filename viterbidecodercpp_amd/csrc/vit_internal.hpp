@@ -33,6 +33,7 @@
 //                    of the stream decode (kernels_dvbt.hpp); behind the decode DVB-T is the DVB-S chain of vit_dvb.hip
 //   vit_is95.hip     the IS-95A forward traffic channel around the K = 9 decode: descrambling, block de-interleaver and the combining of
 //                    the repetitions under the four rate hypotheses in front, the blind rate decision behind (kernels_is95.hpp)
+// arg_rules.hpp states what every unit's argument rule is worded in: overlap, extent, misaligned.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,6 +47,7 @@
 
 #include "../../include/vit_hip.h"
 #include "../../include/vit_hip_experiments.h"
+#include "arg_rules.hpp"
 #include "reg_plan.hpp"
 
 #pragma GCC visibility push(hidden)

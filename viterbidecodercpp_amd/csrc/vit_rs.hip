@@ -30,8 +30,8 @@ const char* rs_decode_invalid(vit_hip_handle h, vit_hip_rs_code code, const uint
     if (frames == 0) return nullptr;
     if (rows > 0x7FFFFFFFu || max_frames > 0x7FFFFFFFu || frames * ((I + RS_TILE - 1) / RS_TILE) > 0x7FFFFFFFu)
         return "more than 2^31 - 1 blocks";
-    const size_t extent = (frames - 1) * (stride ? stride : frame) + frame;
-    if (d_in != d_out && d_in < d_out + extent && d_out < d_in + extent) return "d_out overlaps d_in without being equal";
+    const size_t bytes = extent(frames, stride ? stride : frame, frame);
+    if (d_in != d_out && overlap(d_out, bytes, d_in, bytes)) return "d_out overlaps d_in without being equal";
     return nullptr;
 }
 

@@ -61,7 +61,7 @@ int launch_build(vit_hip_handle h, const void* d_received, const SyncMap& m, con
 
 const char* buffers_invalid(vit_hip_handle h, const void* d_received, const void* d_out) {
     if (!d_received || !d_out) return "NULL buffer";
-    if (h->soft_bytes == 2 && (((uintptr_t)d_received | (uintptr_t)d_out) & 1u)) return "int16 symbols must be 2-byte aligned";
+    if (h->soft_bytes == 2 && (misaligned(d_received, 2) || misaligned(d_out, 2))) return "int16 symbols must be 2-byte aligned";
     return nullptr;
 }
 
@@ -127,7 +127,7 @@ int vit_hip_sync_search(vit_hip_handle h, const void* d_received, size_t n_recei
     if (!d_workspace) return fail(VIT_HIP_ERR_INVALID_ARG, "d_workspace is NULL");
     if (const char* why = buffers_invalid(h, d_received, d_workspace)) return fail(VIT_HIP_ERR_INVALID_ARG, why);
     if (workspace_bytes < lay.total) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (misaligned(d_workspace, 256)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     VIT_HIP_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = (uint8_t*)d_workspace;

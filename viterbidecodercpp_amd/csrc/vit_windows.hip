@@ -33,9 +33,9 @@ const char* extension_invalid(vit_hip_handle h, size_t head, size_t tail) {
 // the caller's buffers of a decode call, `need` the size of its workspace layout
 int check_buffers(vit_hip_handle h, const void* d_symbols, const void* d_workspace, size_t workspace_bytes, size_t need, const void* d_bytes_out) {
     if (!d_symbols || !d_workspace || !d_bytes_out) return fail(VIT_HIP_ERR_INVALID_ARG, "d_symbols/d_workspace/d_bytes_out is NULL");
-    if (h->soft_bytes == 2 && ((uintptr_t)d_symbols & 1u)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
+    if (h->soft_bytes == 2 && misaligned(d_symbols, 2)) return fail(VIT_HIP_ERR_INVALID_ARG, "int16 symbols must be 2-byte aligned");
     if (workspace_bytes < need) return fail(VIT_HIP_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)d_workspace & 255u) != 0) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (misaligned(d_workspace, 256)) return fail(VIT_HIP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     return VIT_HIP_OK;
 }
 
