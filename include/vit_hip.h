@@ -260,8 +260,8 @@ int vit_hip_depuncture_batch(vit_hip_handle h, const void* d_punctured, size_t p
  *     costs more than it hides: one stream, update and chainback back to back. */
 typedef struct vit_hip_pipeline* vit_hip_pipeline_t;
 typedef struct vit_hip_pipeline_schedule {
-    int32_t workspaces;             /* decision workspaces owned (2 or 3) */
-    int32_t update_streams;         /* update kernels that may be in flight at once (1 or 2) */
+    int32_t workspaces;             /* decision workspaces owned (2 or 3 by the rules; vit_hip_pipeline_options: 2 .. 4) */
+    int32_t update_streams;         /* update kernels that may be in flight at once (1 or 2 by the rules; options: up to 3) */
     int32_t chainback_overlapped;   /* 1: chainbacks run on their own stream beside the next update; 0: back to back */
     int32_t chainback_wave_priority;/* 1: the chainback kernel runs at a higher wave priority than the update kernels */
     size_t overlap_max_frames;      /* largest batch whose chainback is overlapped */
@@ -276,7 +276,9 @@ int vit_hip_pipeline_create(vit_hip_handle h, size_t max_frames, size_t L, vit_h
 /* The supported way to pick a schedule other than the library's (A/B measurements, a host that knows what else shares the GPU):
  * every field left at its "rule" value keeps what vit_hip_pipeline_create would choose; the result is what
  * vit_hip_pipeline_get_schedule_v2 reports.  A request the hardware cannot serve (sub-batches for a batch of one wave per SIMD,
- * three update streams without sub-batches) is ignored field by field, never an error.  `want` == NULL: the rules.
+ * three update streams without sub-batches, one update stream for sub-batches -- they are fed from two --, back-to-back chainbacks
+ * under two or three update streams -- there every chainback runs on the one chainback stream) is ignored field by field, never an
+ * error.  `want` == NULL: the rules.  Every row of this contract runs under tests/test_gpu_pipeline_schedules.py.
  * The library reads NO environment variable for its schedules (a build with -DVIT_HIP_EXPERIMENTS does, for scripts/gpu_ab.sh). */
 typedef struct vit_hip_pipeline_options {
     uint32_t struct_size;            /* sizeof(vit_hip_pipeline_options) in the caller's build */
@@ -296,7 +298,8 @@ int vit_hip_pipeline_destroy(vit_hip_pipeline_t p);
 /* schedule_bytes = sizeof(vit_hip_pipeline_schedule) in the CALLER's build: at most that many bytes are written, so a binary
  * built against an older, shorter struct keeps working when the struct grows. */
 int vit_hip_pipeline_get_schedule_v2(vit_hip_pipeline_t p, vit_hip_pipeline_schedule* schedule, size_t schedule_bytes);
-/* legacy entry point: writes the struct as it was when the symbol was introduced (up to and including sub_batch_frames) */
+/* legacy entry point: writes the struct as it was when the symbol was introduced: up to and including `reserved` (the struct
+ * already ended in chainback_small_kernel + reserved then), that is offsetof(reserved) + 4 bytes and nothing behind them */
 int vit_hip_pipeline_get_schedule(vit_hip_pipeline_t p, vit_hip_pipeline_schedule* schedule);
 /* the decision workspace of the most recently submitted (sub-)batch and the frame range of the submitted batch it holds
  * (vit_hip_export_decisions reads the history from it; first_frame / frames may be NULL): valid after a sync() and until the

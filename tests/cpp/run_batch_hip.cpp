@@ -100,6 +100,44 @@ int main() {
         (void)hipFree(d_out2);
     }
 
+    // a schedule of the caller's choosing (vit_hip_pipeline_options: two update streams, four workspaces, chainbacks overlapped --
+    // valid at any batch size) with per-frame end states: nine batches, so every workspace is reused, each with the bytes of the
+    // serial decode from the same end states
+    {
+        std::vector<uint32_t> end_state(frames);
+        for (auto& e : end_state) e = rng.next() % 64;
+        uint32_t* d_es; uint8_t* d_ref; uint8_t* d_out2;
+        const int n_batches = 9;
+        HIP_OK(hipMalloc((void**)&d_es, frames * sizeof(uint32_t)));
+        HIP_OK(hipMalloc((void**)&d_ref, frames * out_bytes));
+        HIP_OK(hipMalloc((void**)&d_out2, n_batches * frames * out_bytes));
+        HIP_OK(hipMemcpy(d_es, end_state.data(), frames * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(d_out2, 0xA5, n_batches * frames * out_bytes));
+        batch.decode(d_sym, frames, L, d_ws, ws_bytes, d_ref, nullptr, nullptr, d_es);
+        HIP_OK(hipDeviceSynchronize());
+        vit_hip_pipeline_options want{};
+        want.struct_size = sizeof(want);
+        want.chainback_overlap = 1; want.update_streams = 2; want.sub_batches = -1; want.workspaces = 4;
+        want.chainback_small_kernel = -1; want.chainback_wave_priority = -1;
+        ViterbiDecoder_HIP_Pipeline<K, R, uint16_t, int16_t> pipe(batch, frames, L, &want);
+        const vit_hip_pipeline_schedule s = pipe.schedule();
+        if (s.update_streams != 2 || s.workspaces != 4 || s.chainback_overlapped != 1 || s.sub_batch_frames != frames) {
+            printf("pipeline options: schedule %d update streams, %d workspaces, overlapped %d\nFAIL\n", s.update_streams, s.workspaces, s.chainback_overlapped);
+            return 1;
+        }
+        for (int r = 0; r < n_batches; r++) pipe.submit(d_sym, frames, d_out2 + size_t(r) * frames * out_bytes, d_es);
+        pipe.sync();
+        std::vector<uint8_t> a(frames * out_bytes), b(frames * out_bytes), plain(frames * out_bytes);
+        HIP_OK(hipMemcpy(a.data(), d_ref, a.size(), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(plain.data(), d_out, plain.size(), hipMemcpyDeviceToHost));
+        if (memcmp(a.data(), plain.data(), a.size()) == 0) { printf("pipeline options: the end states change no byte of the serial decode\nFAIL\n"); return 1; }
+        for (int r = 0; r < n_batches; r++) {
+            HIP_OK(hipMemcpy(b.data(), d_out2 + size_t(r) * frames * out_bytes, b.size(), hipMemcpyDeviceToHost));
+            if (memcmp(a.data(), b.data(), a.size()) != 0) { printf("pipeline options + end states: batch %d differs from the serial decode\nFAIL\n", r); return 1; }
+        }
+        (void)hipFree(d_es); (void)hipFree(d_ref); (void)hipFree(d_out2);
+    }
+
     // one decoder shared by two host threads, as the reference shares one branch table between the Cores of its worker
     // threads (run_benchmark.cpp:193-197): each thread decodes its half of the batch with its own workspace and stream, five
     // times over; the bytes must be those of the single call above (vit_hip.h, "threads")
