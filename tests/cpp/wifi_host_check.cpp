@@ -9,7 +9,8 @@
 // puncturing as a mask walked bit by bit, the scrambler as a shift register stepped bit by bit, the FCS as the reflected CRC-32 bit by
 // bit.  Rates, symbol counts, step counts and lengths include hostile values (above 7, 0xFFFFFFFF).  The one part of the DATA kernel that
 // stays off the host is the __shfl_xor exchange: the lanes of a group run one after the other and the partner's register comes from an
-// array.  The SIGNAL parser is run over all 2^18 fields.
+// array.  The SIGNAL parser is run over all 2^18 fields.  Behind the random shapes come the one-byte de-interleaver shapes with frames in
+// {1, 3, 5, 31, 257} and S in {1, 3, 37, 433}, three times each: two elements behind the last whole dword, and at (1, 1) no whole dword.
 // In front of them: the three argument rules (wifi_deinterleave_invalid, wifi_signal_invalid, wifi_data_invalid) at an accepted call, at
 // every INVALID_ARG case tests/test_gpu_wifi.py sends through the library, and at the zero-work cases.
 #include <stdint.h>
@@ -64,12 +65,16 @@ static uint32_t* per_frame(uint64_t frames, uint64_t stride, uint64_t ordinary) 
     return p;
 }
 
+// what the de-interleaver shapes reached: calls with elements behind the last whole dword, calls with no whole dword
+static uint32_t seen_tails = 0, seen_no_dword = 0;
+
+// a random shape; with force_frames and force_S those two are given and the rest is random
 template <class soft_t>
-static int deint_shape(int it) {
-    const uint64_t frames = 1 + below(below(3) ? 5 : 40), max_sym = 1 + below(4);
+static int deint_shape(int it, uint64_t force_frames = 0, uint64_t force_S = 0) {
+    const uint64_t frames = force_frames ? force_frames : 1 + below(below(3) ? 5 : 40), max_sym = 1 + below(4);
     const bool with_rate = below(3) != 0, with_sym = below(2), with_steps = below(2);
     const uint32_t rate = (uint32_t)below(8);
-    const uint64_t S = 1 + below(below(4) ? max_sym * 216 + 10 : 30), cs = 1 + (below(2) ? 0 : below(6));
+    const uint64_t S = force_S ? force_S : 1 + below(below(4) ? max_sym * 216 + 10 : 30), cs = 1 + (below(2) ? 0 : below(6));
     const uint64_t least = max_sym * (with_rate ? 288 : 48 * N_BPSC[rate]);
     const uint64_t stride_arg = below(2) ? 0 : least + below(7), stride = stride_arg ? stride_arg : max_sym * 288;
     uint32_t* rates = with_rate ? per_frame(frames, cs, 9) : nullptr;
@@ -86,6 +91,8 @@ static int deint_shape(int it) {
 
     const vit::WifiDeintArgs a = vit::wifi_deint_args(in, stride_arg, frames, max_sym, rate, rates, syms, steps, with_rate || with_sym || with_steps ? cs : 0,
                                                       S, out, sizeof(soft_t));
+    seen_tails += a.tail != 0;
+    seen_no_dword += a.groups == 0;
     for (uint32_t b = 0; b < vit::wifi_deint_blocks(a); ++b)
         for (uint32_t t = 0; t < vit::WIFI_BLOCK; ++t) vit::wifi_deint_thread<soft_t>(a, b, t);
 
@@ -299,7 +306,7 @@ struct DataCall {
 
 static int arguments() {
     std::vector<int16_t> d_in(4 * 288), out(4 * 216 * 2 + 8);                           // heap blocks the rules never read
-    std::vector<uint32_t> counts(8);
+    std::vector<uint32_t> counts(32);                                                    // room for the outputs the cases place inside it
     auto plus = [](const void* p, size_t bytes) { return (const void*)((const uint8_t*)p + bytes); };
     DeintCall g;
     g.src = d_in.data(); g.dst = out.data();
@@ -411,6 +418,27 @@ int main(int argc, char** argv) {
         if (it % 2 ? deint_shape<int8_t>(it) : deint_shape<int16_t>(it)) return 1;
         if (data_shape(it)) return 1;
     }
-    printf("ok: %d shapes, all SIGNAL fields, group sizes seen (mask of log2 G) %#x\n", shapes, seen_logG);
+    // the one-byte shapes whose output does not end with a dword: frames and S both odd leave two elements behind the last whole dword,
+    // which threads of block 0 store one by one; one frame of one step has no whole dword at all.  The output ends its heap block: an
+    // element too many is a heap overflow
+    const uint32_t random_tails = seen_tails;
+    static const uint64_t odd_frames[] = {1, 3, 5, 31, 257}, odd_S[] = {1, 3, 37, 433};
+    for (uint64_t frames : odd_frames)
+        for (uint64_t S : odd_S)
+            for (int again = 0; again < 3; ++again) {
+                const uint32_t tails = seen_tails, none = seen_no_dword;
+                if (deint_shape<int8_t>(-1, frames, S)) return 1;
+                if (seen_tails != tails + 1 || (seen_no_dword != none) != (frames == 1 && S == 1)) {
+                    printf("MISMATCH: frames %llu S %llu at one byte: a tail of two and a dword unless both are 1\n", (unsigned long long)frames,
+                           (unsigned long long)S);
+                    return 1;
+                }
+            }
+    if (deint_shape<int16_t>(-1, 1, 1) || deint_shape<int16_t>(-1, 257, 433) || seen_tails != random_tails + 60) {
+        printf("MISMATCH: a tail at two bytes\n");
+        return 1;
+    }
+    printf("ok: %d shapes, all SIGNAL fields, group sizes seen (mask of log2 G) %#x, %u + 60 de-interleaver calls with a tail, %u without a dword\n", shapes,
+           seen_logG, random_tails, seen_no_dword);
     return 0;
 }

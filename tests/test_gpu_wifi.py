@@ -331,6 +331,13 @@ def test_the_whole_chain_on_64_ppdus():
     assert np.array_equal(psdu.cpu().numpy(), image)
 
 
+@functools.lru_cache(maxsize=None)
+def side_stream():
+    """the one stream the graph tests of the 802.11a/g route warm up on: created once, so that they take one stream from torch's pool"""
+    import torch
+    return torch.cuda.Stream()
+
+
 def test_the_chain_captured_into_a_graph():
     import torch
     wifi = WifiDecoder(decoder("SOFT16"), decoder("SOFT16"), CHAIN_MAX_SYM)
@@ -338,7 +345,7 @@ def test_the_chain_captured_into_a_graph():
     d_signal, d_data = torch.from_numpy(first[0].copy()).cuda(), torch.from_numpy(first[1].copy()).cuda()
     out = (torch.empty(first[2].shape, dtype=torch.uint8, device="cuda"), torch.empty((64, 4), dtype=torch.int32, device="cuda"),
            torch.empty((64, 5), dtype=torch.int32, device="cuda"))
-    side = torch.cuda.Stream()
+    side = side_stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         wifi.decode(d_signal, d_data, out=out)                     # warm-up outside the capture: every buffer is allocated here
