@@ -3,7 +3,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Itests/cpp/hip_stub -o dvbt_host_check dvbt_host_check.cpp
 //   ./dvbt_host_check [shapes = 90] [seed = 1]
 // It checks, with no GPU: the compile-time tables against H built from lists of bits, with the check values of include/vit_hip.h; the
-// multiply-and-shift divisions over every value a unit can hold; the workgroup remap as a bijection; every INVALID_ARG case of the
+// multiply-and-shift divisions over every value a unit can hold; the workgroup remap as a bijection onto (row, symbol, unit) at the units
+// of every mode, several rows and symbols and every remainder of the block count mod 8; every INVALID_ARG case of the
 // argument rule and the zero-work cases; and random shapes of every mode, v, rate and symbol width whose input ends its heap block and
 // whose output rows sit in a pitch with guard elements: every thread of the grid runs through the kernel's own functions, and every
 // byte of the output buffer is compared with the transmit side walked literally -- puncture, demultiplex, bit-interleave, symbol-
@@ -106,6 +107,25 @@ static int tables() {
             if (p.row != 0 || p.unit != 0 || p.y >= blocks || seen[p.y]++) { printf("MISMATCH: remap of %u blocks at %u\n", blocks, b); return 1; }
         }
     }
+    // the same with the units of a real mode, several rows and symbols: every (row, y, unit) exactly once.  The shapes of
+    // tests/test_gpu_dvbt_edges.py first -- blocks & 7 takes every value 0 .. 7, blocks below 8 and from 64 on -- then more of 4k and 8k
+    static const uint32_t SHAPES[][3] = {{3, 1, 1}, {3, 5, 1}, {3, 7, 1}, {3, 3, 5}, {3, 2, 4}, {3, 9, 3}, {3, 11, 5}, {3, 64, 1}, {3, 67, 3},
+                                         {6, 1, 1}, {6, 3, 3}, {12, 1, 1}, {3, 2, 3}, {3, 13, 6}, {6, 5, 3}, {6, 7, 2}, {6, 13, 9}, {12, 2, 68}, {12, 5, 3}, {12, 7, 5}};
+    uint32_t low = 0;
+    for (const auto& s : SHAPES) {
+        vit::DvbtArgs a{};
+        a.units = s[0]; a.rows = s[1]; a.n_sym = s[2]; a.blocks = s[0] * s[1] * s[2];
+        low |= 1u << (a.blocks & 7u);
+        std::vector<int> seen(a.blocks, 0);
+        for (uint32_t b = 0; b < a.blocks; ++b) {
+            const vit::DvbtPlace p = vit::dvbt_place(a, b);
+            if (p.row >= a.rows || p.y >= a.n_sym || p.unit >= a.units || seen[(p.row * a.n_sym + p.y) * a.units + p.unit]++) {
+                printf("MISMATCH: remap of %u rows x %u symbols x %u units at block %u: row %u y %u unit %u\n", s[1], s[2], s[0], b, p.row, p.y, p.unit);
+                return 1;
+            }
+        }
+    }
+    if (low != 0xFFu) { printf("MISMATCH: the remap shapes leave a remainder out: %02x\n", low); return 1; }
     return 0;
 }
 

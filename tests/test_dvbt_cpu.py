@@ -1,7 +1,9 @@
 """viterbidecodercpp_amd/dvbt.py against the check values of include/vit_hip.h and the independent restatement of tests/dvbt_reference.py
 at every mode, constellation, rate and parity; the transmit side undone by the receive rule; the spot rule; the steps per symbol; the
 argument errors of the Python layer and the one the ABI reports without a device; and the kernel's own source with its argument rule run
-on the host as a program of its own (tests/cpp/dvbt_host_check.cpp).  No GPU."""
+on the host as a program of its own (tests/cpp/dvbt_host_check.cpp); and the case builders the GPU tests share (tests/dvbt_cases.py):
+transmit() against the checksums of the values it had when it was part of tests/test_gpu_dvbt.py, its parity and decode type, the SNR
+table against the standard's figures.  No GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -96,6 +98,51 @@ def test_argument_errors():
                 lambda: dvbt_interleave_numpy(np.zeros(3023), "2k", 2), lambda: dvbt_steps_per_symbol("2k", 2, -1)):
         with pytest.raises(ValueError):
             bad()
+
+
+# CRC-32 of (transport packets, soft bits) of transmit(mode, v, rate, 24, 11 + rate, SOFT16) noise-free and at (SNR_DB[rate], NOISE_SEED +
+# rate), recorded when transmit() was part of tests/test_gpu_dvbt.py: the inputs of that file's chains
+TRANSMIT_CRC = {("2k", 2, 0): ((26, 3024), 0xFD7D6650, 0xE57C7C4A, 0x62F1262E), ("2k", 2, 2): ((18, 3024), 0x4A565BD1, 0xA6AFB1C1, 0x851F051D),
+                ("2k", 6, 4): ((5, 9072), 0xE3A3F9CF, 0xAFB00E58, 0xC017400E)}
+
+
+def test_the_shared_transmit_side_is_the_recorded_one():
+    import zlib
+
+    from viterbidecodercpp_amd import get_decoding_config
+    from tests import dvbt_cases as cases
+    pc = get_decoding_config("SOFT16", 2)
+    assert (cases.AMPLITUDE, cases.NOISE_SEED, cases.FORNEY_DELAY) == (48, 2024, 11)
+    assert cases.SNR_DB == {0: 1.5, 1: 3.25, 2: 4.25, 3: 5.2, 4: 5.8}
+    # EN 300 421 table 5: Eb/N0 for quasi-error-free reception by rate, plus 10 log10 of the rate, to the 0.05 dB the table is good for
+    for rate, ebn0 in enumerate((4.5, 5.0, 5.5, 6.0, 6.4)):
+        k, n = DVBT_RATES[rate]
+        assert abs(cases.SNR_DB[rate] - (ebn0 + 10 * np.log10(k / n))) < 0.03, rate
+    for (mode, v, rate), (shape, crc_ts, crc_clean, crc_noisy) in TRANSMIT_CRC.items():
+        ts, clean = cases.transmit(mode, v, rate, 24, 11 + rate, pc)
+        ts2, noisy = cases.transmit(mode, v, rate, 24, 11 + rate, pc, cases.SNR_DB[rate], cases.NOISE_SEED + rate)
+        assert clean.shape == noisy.shape == shape and clean.dtype == noisy.dtype == np.int16 and ts.shape == (24, 188) and np.array_equal(ts, ts2)
+        assert (zlib.crc32(ts.tobytes()), zlib.crc32(clean.tobytes()), zlib.crc32(noisy.tobytes())) == (crc_ts, crc_clean, crc_noisy), (mode, v, rate)
+
+
+def test_the_shared_transmit_side_by_parity_and_decode_type():
+    from viterbidecodercpp_amd import get_decoding_config
+    from tests import dvbt_cases as cases
+    pc = get_decoding_config("SOFT16", 2)
+    ts, even = cases.transmit("2k", 4, 3, 4, 7, pc)
+    ts1, odd = cases.transmit("2k", 4, 3, 4, 7, pc, parity=1)
+    assert np.array_equal(ts, ts1) and even.shape == odd.shape and not np.array_equal(even, odd)
+    steps = dvbt_deinterleave_numpy(even, "2k", 4, 3, 0)
+    assert np.array_equal(steps, dvbt_deinterleave_numpy(odd, "2k", 4, 3, 1)) and not np.array_equal(steps, dvbt_deinterleave_numpy(odd, "2k", 4, 3, 0))
+    assert np.array_equal(cases.transmit("2k", 4, 3, 4, 7, None, decode_type="SOFT16")[1], even)
+    for decode_type, dtype, high in (("SOFT8", np.int8, None), ("HARD8", np.int8, 1)):
+        levels = get_decoding_config(decode_type, 2)
+        soft = cases.transmit("2k", 4, 3, 4, 7, None, decode_type=decode_type)[1]
+        assert soft.dtype == dtype and (high is None or levels.soft_decision_high == high)
+        assert np.array_equal(soft > 0, even > 0) and set(np.unique(soft)) == {levels.soft_decision_low, levels.soft_decision_high}
+    # the host chain, noise-free, from either parity: 13 packets of 24 is a decode of 40 000 steps, so 12 packets of a short stream
+    packets, status = cases.host_chain(cases.transmit("2k", 6, 4, 12, 8, pc, parity=1)[1], "2k", 6, 4, 12, parity=1)
+    assert (status == 0).all() and np.array_equal(packets, cases.transmit("2k", 6, 4, 12, 8, pc)[0][:1])
 
 
 def test_the_abi_reports_a_null_handle_without_a_device():

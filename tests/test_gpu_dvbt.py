@@ -3,18 +3,19 @@ independent restatement of tests/dvbt_reference.py, on every byte of the output 
 row included: all 3 modes x v in {2, 4, 6} x 5 rates, both first parities, both symbol widths, n_sym in {1, 2, 3}, rows in {1, 3} at an
 input stride and an output pitch of their own; the parity counters across two calls and in a captured graph replayed twice; every
 rejected argument with a live handle; and the whole chain from transport packets to DvbtDecoder.take_frames(), noise-free and in white
-Gaussian noise at an SNR at which the chain by the host rules, run on the CPU first, recovers every packet."""
+Gaussian noise at an SNR at which the chain by the host rules, run on the CPU first, recovers every packet.  The transmit side and the
+host chain are in tests/dvbt_cases.py.  tests/test_gpu_dvbt_edges.py goes on from here: every remainder of the workgroup remap with up
+to 67 rows, a frame of 68 symbols, HARD8, each counter array alone, and DvbtDecoder with lockstep streams, parity=1, the cuts, 4k and 8k,
+16-QAM, 2/3 and 5/6, 8-bit symbols and its rejections."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
-from viterbidecodercpp_amd import (COMMON_CODES, DVB_INTERLEAVER, DVB_RS_204_188, DVBT_MODES, BatchDecoder, DvbtDecoder, _lib, conv_deinterleave_numpy,
-                                   conv_interleave_numpy, dvb_derandomize_numpy, dvb_randomize_numpy, dvbt_deinterleave_numpy, dvbt_interleave_numpy,
-                                   dvbt_puncture_numpy, dvbt_steps_per_symbol, rs_decode_numpy, rs_encode_numpy)
-from viterbidecodercpp_amd.synth import encode_bits_numpy
+from viterbidecodercpp_amd import COMMON_CODES, DVBT_MODES, BatchDecoder, _lib, dvbt_deinterleave_numpy, dvbt_steps_per_symbol
 from tests import dvbt_reference as ref
+from tests.dvbt_cases import NOISE_SEED, SNR_DB, host_chain, receive, transmit
 from tests.helpers import make_table_config
 
 pytestmark = pytest.mark.gpu
@@ -178,84 +179,8 @@ def test_rejected_arguments_launch_nothing():
     assert (d_out[2 * 2 * 3024:].view(torch.uint8) == FILL).all()
 
 
-AMPLITUDE = 48          # of a soft bit under noise: 127 is 2.8 sigma away at the lowest SNR used, so few values clip and magnitudes are real
-
-
-def transmit(mode, v, rate, n_packets, seed, pc, snr_db=None, noise_seed=None):
-    """random transport packets -> energy dispersal, RS(204,188), Forney (12, 17), the package's encoder rule, puncturing, the inner
-    interleaver -> soft bits [n_sym][Nmax * v] from symbol parity 0, the last symbol padded with random bits.  Noise-free they are
-    high / low; with snr_db every soft bit is AMPLITUDE (+-1 + n), n white Gaussian of variance 1 / (2 snr) -- snr = Es/N0 of one sent
-    bit -- from noise_seed, rounded and clipped to [low, high]"""
-    rng = np.random.default_rng(seed)
-    ts = rng.integers(0, 256, size=(n_packets, 188), dtype=np.uint8)
-    ts[:, 0] = 0x47
-    sent = conv_interleave_numpy(rs_encode_numpy(DVB_RS_204_188, dvb_randomize_numpy(ts), 1), *DVB_INTERLEAVER)
-    steps = dvbt_steps_per_symbol(mode, v, rate)
-    bits = np.unpackbits(sent.reshape(-1))
-    n_sym = -(-(bits.size + 6) // steps)
-    bits = np.concatenate([bits, rng.integers(0, 2, size=n_sym * steps - bits.size, dtype=np.uint8)])
-    coded = encode_bits_numpy(7, 2, COMMON_CODES[2].G, np.packbits(bits))[0, :bits.size]
-    cells = dvbt_interleave_numpy(dvbt_puncture_numpy(coded, rate), mode, v, 0)
-    if snr_db is None:
-        return ts, np.where(cells != 0, pc.soft_decision_high, pc.soft_decision_low).astype(pc.soft_dtype)
-    sigma = np.sqrt(0.5 / 10.0 ** (snr_db / 10.0))
-    noisy = np.where(cells != 0, 1.0, -1.0) + sigma * np.random.default_rng(noise_seed).standard_normal(cells.shape)
-    return ts, np.clip(np.rint(AMPLITUDE * noisy), pc.soft_decision_low, pc.soft_decision_high).astype(pc.soft_dtype)
-
-
-def viterbi_numpy(steps):
-    """the host rule of the decode: the maximum-likelihood path of the stock K = 7 code from the zero state through steps [n][2] (0 an
-    erasure), by correlation in int64, chained back from the best final state -> bits uint8 [n]"""
-    new = np.arange(64)
-    reg = new[:, None] | (np.arange(2)[None, :] << 6)               # [new state][oldest bit]: bit k is the input of k steps ago
-    prev = reg >> 1
-    sign = np.stack([2 * (sum((reg & g) >> k & 1 for k in range(7)) & 1) - 1 for g in COMMON_CODES[2].G], axis=-1).astype(np.int64)
-    y = np.asarray(steps).astype(np.int64)
-    branch = sign[None, :, :, 0] * y[:, None, None, 0] + sign[None, :, :, 1] * y[:, None, None, 1]
-    metric = np.full(64, -1 << 40, dtype=np.int64)
-    metric[0] = 0
-    chose = np.empty((len(y), 64), dtype=np.uint8)
-    for t in range(len(y)):
-        cand = metric[prev] + branch[t]
-        chose[t] = cand[:, 1] > cand[:, 0]
-        metric = cand.max(axis=1)
-    state, bits, prev, chose = int(metric.argmax()), np.empty(len(y), dtype=np.uint8), prev.tolist(), chose.tolist()
-    for t in range(len(y) - 1, -1, -1):
-        bits[t] = state & 1
-        state = prev[state][chose[t][state]]
-    return bits
-
-
-def host_chain(soft, mode, v, rate, n_packets):
-    """the receive chain by the host rules alone: dvbt_deinterleave_numpy, the decode, the Forney de-interleaver, RS(204,188), energy
-    dispersal.  The stream starts at a packet, so the host needs no sync search -> (packets [n_packets - 11][188], rs_status)"""
-    bits = viterbi_numpy(dvbt_deinterleave_numpy(soft, mode, v, rate, 0))
-    frames = np.packbits(bits[:n_packets * 1632]).reshape(n_packets, 204)
-    frames, status = rs_decode_numpy(DVB_RS_204_188, conv_deinterleave_numpy(frames, *DVB_INTERLEAVER)[0])
-    return dvb_derandomize_numpy(frames, 0)[0], status.reshape(-1)
-
-
-def receive(dec, mode, v, rate, soft, cuts):
-    """soft [n_sym][Nmax * v] through a DvbtDecoder in pushes cut at `cuts` -> (packets, rs_status) of all its take_frames()"""
-    import torch
-    d = torch.from_numpy(soft).cuda()
-    rx = DvbtDecoder(dec, mode, v, rate, window=1024)
-    packets, status = [], []
-    edges = [0] + [c for c in cuts if c < len(soft)] + [len(soft)]
-    for a, b in zip(edges[:-1], edges[1:]):
-        rx.finish(d[a:b]) if b == len(soft) else rx.push(d[a:b])
-        got = rx.take_frames()
-        packets.append(got[0]), status.append(got[2])
-    return np.concatenate(packets), np.concatenate(status).reshape(-1)
-
-
 CHAIN = [("2k", 2, 0, [13, 14, 21]), ("2k", 2, 2, [9, 16]), ("2k", 6, 4, [3, 4])]
 CHAIN_IDS = ["qpsk-1/2", "qpsk-3/4", "64qam-7/8"]
-# Es/N0 of one sent soft bit in dB, by rate index: where EN 300 421 table 5 puts quasi-error-free reception of this inner code behind
-# RS(204,188) -- Eb/N0 of 4.5, 5.5 and 6.4 dB at 1/2, 3/4 and 7/8, less 10 log10 of the rate's reciprocal.  The channel bit error rate is
-# 4.4 %, 1.0 % and 0.26 %, and what the decode leaves is Reed-Solomon's to correct.  The host-rule chain recovers every packet there
-SNR_DB = {0: 1.5, 2: 4.25, 4: 5.8}
-NOISE_SEED = 2024
 
 
 @pytest.mark.parametrize("mode,v,rate,cuts", CHAIN, ids=CHAIN_IDS)
