@@ -1208,6 +1208,102 @@ int vit_hip_is95_rate_decide_batch(vit_hip_handle h, const uint8_t* const d_byte
                                    const uint32_t* const d_syndrome[2], size_t frames, const uint32_t max_ser_num[4], uint32_t ser_den,
                                    vit_hip_is95_decision* d_decision, uint8_t* d_info, size_t info_stride, vit_hip_stream_t stream);
 
+/* ---- GSM channel decoding: burst de-interleaver, the Fire code of the control channels, TCH/FS frames -----------------------------------
+ * GSM (3GPP TS 45.003, formerly GSM 05.03) protects its control channels (SACCH, BCCH, CCCH, SDCCH, FACCH; the CS-1 layout) and full-rate
+ * speech (TCH/FS) with the K = 5, R = 1/2 code G0 = 1 + D^3 + D^4, G1 = 1 + D + D^3 + D^4 and spreads a block of 456 coded bits over the
+ * 114 payload bits of 4 or 8 bursts.  These calls stand around vit_hip_decode_batch on a handle of K = 5, R = 2; none of them depends on the
+ * polynomials.  The constants are written from memory of TS 45.003 clauses 3.1, 4.1 and 4.3; what is stated HERE is the rule.
+ * POLYNOMIALS.  In this ABI bit k of a polynomial taps the input of k steps ago: the GSM code is (25, 27) = (0b11001, 0b11011), not the
+ * stock "Basic K=5 R=1/2" (23, 25); the input bits 1 0 0 0 0 encode to the pairs 11 01 00 11 11.  The GENERIC K = 5 kernels serve it.
+ *
+ * vit_hip_gsm_deinterleave_batch: bursts -> the symbols vit_hip_decode_batch reads; soft_t is the handle's symbol type.
+ *   - input: `rows` rows of `bursts` bursts, one row per logical channel: burst B of row r is the 116 soft_t e(B, 0 .. 115) at d_in + r *
+ *     in_row_stride + B * in_burst_stride (elements; in_burst_stride 0 => 116, in_row_stride 0 => bursts * the burst stride), the two
+ *     half-bursts of 57 with the stealing flags hl = e(B, 57) and hu = e(B, 58) between them.  bursts is a multiple of 4 = 4 m;
+ *   - flags VIT_HIP_GSM_NEGATE: every value read from d_in or d_hist_in is negated on the way, in int32, and clamped to the range of soft_t
+ *     (-(-128) is 127): for demodulators that send bit 1 as the negative value, or a caller who folds the A5 keystream into the sign
+ *     beforehand.  An erasure at a midpoint of 0 stays one;
+ *   - the map: coded bit k = 0 .. 455 of block n is payload position j(k) = 2 ((49 k) mod 57) + ((k mod 8) div 4) of burst B, read as
+ *     e(B, j) for j < 57 and e(B, j + 2) for j >= 57.  j(0 .. 7) = 0, 98, 82, 66, 51, 35, 19, 3.
+ *     mode VIT_HIP_GSM_BLOCK: B = 4 n + (k mod 4); a bijection onto 4 x 114; no history; every row gives m blocks.
+ *     mode VIT_HIP_GSM_DIAGONAL (TCH/F, FACCH/F): B = 4 n + (k mod 8) in the SEQUENCE of the row: the four bursts of d_hist_in + r * 464
+ *     where d_hist_in is given and d_fill_in[r] == 4, then the input.  The first four bursts of a block carry its even j, the last four
+ *     its odd j, 57 each.  A row with history gives m blocks, one without m - 1, compacted to the front of the row's m slots; the slots
+ *     behind them are written as zeros (d_steal too), so every byte of every output is defined;
+ *   - the carried state, diagonal mode only: d_hist_out + r * 464 receives the last four bursts of the row's input AS RECEIVED (not
+ *     negated; a call with the flag negates them when it reads them) and d_fill_out[r] = 4.  d_hist_in / d_fill_in and d_hist_out /
+ *     d_fill_out come in pairs, each pair may be NULL, and they travel between two sets of arrays from call to call like the history of
+ *     vit_hip_dab_deinterleave_batch, so a captured graph of two calls replays correctly.  d_fill_in[r] other than 4 means no history;
+ *   - d_n_out (may be NULL), uint32 [rows]: the blocks row r gave: m, or m - 1;
+ *   - outputs, any of them NULL but not all four: d_full [rows][m][228][2] soft_t, coded bit k at [k / 2][k % 2]: what the decode reads with
+ *     L = 224 (xCCH, FACCH: 184 data + 40 parity bits, 4 tail bits); d_class1 [rows][m][189][2], coded bits 0 .. 377: with L = 185 (TCH/FS);
+ *     d_class2 [rows][m][78], coded bits 378 .. 455; d_steal int32 [rows][m]: the sum of the block's stealing flags after the optional
+ *     negation -- hu of the first four bursts plus hl of the last four in diagonal mode, all eight flags of the four bursts in block mode.
+ *     The caller thresholds it to tell FACCH from speech.
+ * Nothing outside the 116 elements of a burst and the 464 of a row's history is read.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle or d_in, d_full, d_class1, d_class2
+ * and d_steal all NULL, a handle with R != 2, mode above VIT_HIP_GSM_DIAGONAL, flags other than VIT_HIP_GSM_NEGATE, any of the four history
+ * arguments in block mode, d_hist_in without d_fill_in or d_hist_out without d_fill_out (and the reverse), bursts no multiple of 4, a
+ * symbol buffer not aligned to soft_t, a count array or d_steal not aligned to 4 bytes, a non-zero in_burst_stride below 116 or
+ * in_row_stride below a row's bursts, rows, bursts, rows * m or a stride at or above 2^31 - 1, an output (d_hist_out, d_fill_out and d_n_out
+ * included) that overlaps another or d_in, d_hist_in or d_fill_in.  rows = 0 or bursts = 0 returns VIT_HIP_OK with no work.
+ *
+ * vit_hip_gsm_fire_batch: the Fire code (224, 184) of the control channels, g(D) = (D^23 + 1)(D^17 + D^3 + 1) = D^40 + D^26 + D^23 + D^17 +
+ * D^3 + 1 = 0x10004820009.
+ *   - input: frame f is the 28 bytes at d_bytes + f * bytes_frame_stride (0 => 28), bit u(t), t = 0 .. 223, being bit 7 - t%8 of byte t/8 as
+ *     vit_hip_decode_batch writes them with L = 224: the 184 data bits d first, then the 40 parity bits;
+ *   - syndrome = (r mod g) XOR (2^40 - 1) with r(D) = sum of u(t) D^(223 - t): the standard makes the remainder all ones.  184 zero data
+ *     bits carry 40 parity ones; an error in u(223) alone gives syndrome 1, one in u(183) alone 0x0004820009;
+ *   - max_burst = 0 .. 12 (0: detect only).  Syndrome 0: status 0.  Otherwise the call looks for THE error pattern p(D) D^m with p(0) = 1,
+ *     deg p < max_burst, m >= 0 and m + deg p <= 223 whose remainder mod g is the syndrome: p = syndrome D^(-m) mod g.  All 438 271 patterns
+ *     of length <= 12 inside 224 bits have distinct non-zero syndromes, so there is at most one.  Found: its bits are flipped, status = deg
+ *     p + 1 (the burst's length), first_bit = 223 - m - deg p (the first flipped t).  Not found: status = -1, first_bit = 0 and the bits go
+ *     out as received.  A frame with more errors than one burst may be "corrected" to another codeword: the code's limit, not the call's;
+ *   - d_status[f] = {status, first_bit, syndrome_lo, syndrome_hi}: the syndrome as received, bits 0 .. 31 and 32 .. 39;
+ *   - d_data + f * data_stride (0 => 23): the 23 data bytes, d(8 i + b) as bit 7 - b of byte i -- or, with VIT_HIP_GSM_LSB_FIRST, as bit b,
+ *     the octet order of GSM 04.04.  In place is allowed: d_data == d_bytes with the same (resolved) stride.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_bytes, d_status or d_data,
+ * max_burst above 12, flags other than VIT_HIP_GSM_LSB_FIRST, d_status not aligned to 4 bytes, a non-zero bytes_frame_stride below 28 or
+ * data_stride below 23, frames or a stride at or above 2^31 - 1, d_status overlapping d_bytes or d_data, d_data overlapping d_bytes other
+ * than in place.  frames = 0 returns VIT_HIP_OK with no work.
+ *
+ * vit_hip_gsm_tchfs_batch: decoded class I bits and class II soft bits -> 260-bit speech frames.
+ *   - input: frame f is the 24 bytes at d_bytes + f * bytes_frame_stride (0 => 24), u(0 .. 184) as vit_hip_decode_batch writes them with L =
+ *     185, and the 78 soft_t at d_class2 + f * 78, what the de-interleaver wrote;
+ *   - d(2 k) = u(k) and d(2 k + 1) = u(184 - k) for k = 0 .. 90; p(k) = u(91 + k), k = 0, 1, 2; d(182 + k) = 1 where 2 c > high + low for
+ *     class II value c = d_class2[f][k] and the handle's soft_decision_high / low, the rule of vit_hip_channel_errors_batch; a value at the
+ *     midpoint gives 0 and is counted;
+ *   - d_speech + f * speech_stride (0 => 33): 33 bytes, d(t) as bit 7 - t%8 of byte t/8, the last four bits 0;
+ *   - d_status[f] (d_status may be NULL) = {parity_syndrome, class2_erasures}: the 3 bits (d(0 .. 49) D^3 + p(0) D^2 + p(1) D + p(2)) mod (D^3 +
+ *     D + 1), XORed with 7 -- 0 where the parity holds: vit_hip_crc_batch's (3, 0x3, 0, 0x7) over d(0 .. 49) --, and the class II values at
+ *     the midpoint.
+ * Errors: VIT_HIP_ERR_INVALID_ARG, with nothing launched and the outputs untouched, for a NULL handle, d_bytes, d_class2 or d_speech,
+ * d_class2 not aligned to soft_t or d_status to 4 bytes, a non-zero bytes_frame_stride below 24 or speech_stride below 33, frames or a stride
+ * at or above 2^31 - 1, an output that overlaps an input or the other output.  frames = 0 returns VIT_HIP_OK with no work.
+ * Batch calls like the others: each enqueues ONE kernel on `stream` and no memset (memset nodes of a replayed graph have produced wrong
+ * counts on this runtime: see the IS-95 error counts above), allocates nothing, needs no workspace, synchronises nothing, always writes
+ * every element of every non-NULL output and can be captured into a hipGraph: de-interleave, decode, Fire is the control-channel
+ * receiver, de-interleave, two decodes, TCH/FS and Fire the TCH/F one.
+ * Out of scope: GPRS CS-2..4 and EGPRS (puncturing tables, USF precoding); TCH/HS, EFR's preliminary CRC-8, AMR; SACCH/TCH multiframe
+ * scheduling and deciphering (the caller negates with the A5 keystream); burst demodulation; per-row burst counts in one call; a
+ * transmitter on the card.  SCH, RACH and the TCH/FS parity alone need no call of their own: vit_hip_crc_batch with (10, 0x175, 0, 0x3FF),
+ * (6, 0x2F, 0, 0x3F) -- the syndrome is the BSIC -- and (3, 0x3, 0, 0x7). */
+#define VIT_HIP_GSM_BLOCK 0u
+#define VIT_HIP_GSM_DIAGONAL 1u
+#define VIT_HIP_GSM_NEGATE 1u       /* flags of vit_hip_gsm_deinterleave_batch */
+#define VIT_HIP_GSM_LSB_FIRST 1u    /* flags of vit_hip_gsm_fire_batch */
+typedef struct vit_hip_gsm_fire { int32_t status; uint32_t first_bit, syndrome_lo, syndrome_hi; } vit_hip_gsm_fire;
+typedef struct vit_hip_gsm_tchfs { uint32_t parity_syndrome, class2_erasures; } vit_hip_gsm_tchfs;
+int vit_hip_gsm_deinterleave_batch(vit_hip_handle h, const void* d_in, size_t in_row_stride, size_t in_burst_stride, size_t rows, size_t bursts,
+                                   unsigned mode, unsigned flags, const void* d_hist_in, const uint32_t* d_fill_in, void* d_hist_out,
+                                   uint32_t* d_fill_out, uint32_t* d_n_out, void* d_full /* [rows][bursts / 4][228][2] soft_t, or NULL */,
+                                   void* d_class1 /* [rows][bursts / 4][189][2] */, void* d_class2 /* [rows][bursts / 4][78] */,
+                                   int32_t* d_steal /* [rows][bursts / 4] */, vit_hip_stream_t stream);
+int vit_hip_gsm_fire_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_frame_stride, size_t frames, unsigned max_burst,
+                           unsigned flags, vit_hip_gsm_fire* d_status, uint8_t* d_data, size_t data_stride, vit_hip_stream_t stream);
+int vit_hip_gsm_tchfs_batch(vit_hip_handle h, const uint8_t* d_bytes, size_t bytes_frame_stride, const void* d_class2, size_t frames,
+                            uint8_t* d_speech, size_t speech_stride, vit_hip_gsm_tchfs* d_status, vit_hip_stream_t stream);
+
 /* The clock the SIMDs sustain under the update kernels' instruction class, measured on the device: every SIMD runs four waves
  * of independent v_pk_add_u16 for about 2 ms between readings of s_memtime (shader clocks) and s_memrealtime (constant
  * reference clock); *mhz_out = their median ratio x the reference rate.  *cycles_per_pk_instr_out (may be NULL) = shader

@@ -372,6 +372,34 @@ public:
                                              ser_den, d_decision, d_info, info_stride, stream),
               "vit_hip_is95_rate_decide_batch");
     }
+    // GSM channel decoding (vit_hip_gsm_deinterleave_batch / vit_hip_gsm_fire_batch / vit_hip_gsm_tchfs_batch; 3GPP TS 45.003), a decoder of
+    // K = 5, R = 2 with the polynomials (25, 27).  gsm_deinterleave reads `rows` rows of `bursts` = 4 m bursts of 116 soft_t (stealing flags
+    // at 57 and 58) and undoes the block (mode VIT_HIP_GSM_BLOCK) or the diagonal (VIT_HIP_GSM_DIAGONAL: 8 bursts a block, four bursts of
+    // history per row ping-ponged between d_hist_in / d_fill_in and d_hist_out / d_fill_out) interleaver: d_full [rows][m][228][2] is what
+    // decode reads with total_bits = 224, d_class1 [rows][m][189][2] with 185, d_class2 [rows][m][78] the uncoded bits, d_steal [rows][m] the
+    // sum of the stealing flags, d_n_out [rows] the blocks a row gave (m, or m - 1 without history); any output may be nullptr, not all
+    // four.  gsm_fire checks the 40-bit Fire code of 28 decoded bytes a frame, corrects one error burst of at most max_burst <= 12 bits
+    // and writes {status (0 clean, 1 .. 12 the burst corrected, -1 not correctable), first_bit, syndrome} and the 23 data bytes (in place
+    // allowed; VIT_HIP_GSM_LSB_FIRST: octets LSB-first).  gsm_tchfs makes the 260-bit speech frame (33 bytes) of the 24 decoded class I
+    // bytes and the 78 class II soft bits, with {parity_syndrome, class2_erasures}.
+    void gsm_deinterleave(const soft_t* d_in, size_t rows, size_t bursts, unsigned mode, soft_t* d_full, soft_t* d_class1 = nullptr,
+                          soft_t* d_class2 = nullptr, int32_t* d_steal = nullptr, uint32_t* d_n_out = nullptr, unsigned flags = 0,
+                          const soft_t* d_hist_in = nullptr, const uint32_t* d_fill_in = nullptr, soft_t* d_hist_out = nullptr,
+                          uint32_t* d_fill_out = nullptr, size_t in_row_stride = 0, size_t in_burst_stride = 0, void* stream = nullptr) {
+        check(vit_hip_gsm_deinterleave_batch(m_hip, d_in, in_row_stride, in_burst_stride, rows, bursts, mode, flags, d_hist_in, d_fill_in,
+                                             d_hist_out, d_fill_out, d_n_out, d_full, d_class1, d_class2, d_steal, stream),
+              "vit_hip_gsm_deinterleave_batch");
+    }
+    void gsm_fire(const uint8_t* d_bytes, size_t frames, vit_hip_gsm_fire* d_status, uint8_t* d_data, unsigned max_burst = 12,
+                  unsigned flags = 0, size_t bytes_frame_stride = 0, size_t data_stride = 0, void* stream = nullptr) {
+        check(vit_hip_gsm_fire_batch(m_hip, d_bytes, bytes_frame_stride, frames, max_burst, flags, d_status, d_data, data_stride, stream),
+              "vit_hip_gsm_fire_batch");
+    }
+    void gsm_tchfs(const uint8_t* d_bytes, const soft_t* d_class2, size_t frames, uint8_t* d_speech, vit_hip_gsm_tchfs* d_status = nullptr,
+                   size_t bytes_frame_stride = 0, size_t speech_stride = 0, void* stream = nullptr) {
+        check(vit_hip_gsm_tchfs_batch(m_hip, d_bytes, bytes_frame_stride, d_class2, frames, d_speech, speech_stride, d_status, stream),
+              "vit_hip_gsm_tchfs_batch");
+    }
     // multi-GPU set-up: the shared branch table and config travel once from rank `root` to every rank of an RCCL
     // communicator (ncclComm_t); each rank then constructs its own decoder from its copy.  The other ranks pass a table
     // built from any polynomials (it is overwritten) -- the reference shares one table between decoders (README.md:14)

@@ -2,7 +2,7 @@
 
 Product code: csrc/ (HIP kernels + C ABI, built to libvit_hip.so) and the host-side mirror of the reference's decoder
 interface in decoder.py -- the outer chain behind the decoder (marker search, frame extraction, Reed-Solomon, de-interleaver,
-derandomiser, frame check) in outer.py, the tensor rules of both in _args.py --, with the chunked stream receivers in stream.py the LTE rate matching in front of the tail-biting decode in lte.py and the DAB profiles, interleaver and dispersal in dab.py, the DAB+ superframes behind them in dabplus.py, the 802.11a/g OFDM data path in wifi.py, the DVB-T inner de-interleaver and its receiver in dvbt.py, the IS-95A forward traffic channel (de-interleave, combine, blind rate decision) in is95.py.  codes.py / synth.py hold constants and synthetic-input generation for the measurement.
+derandomiser, frame check) in outer.py, the tensor rules of both in _args.py --, with the chunked stream receivers in stream.py the LTE rate matching in front of the tail-biting decode in lte.py and the DAB profiles, interleaver and dispersal in dab.py, the DAB+ superframes behind them in dabplus.py, the 802.11a/g OFDM data path in wifi.py, the DVB-T inner de-interleaver and its receiver in dvbt.py, the IS-95A forward traffic channel (de-interleave, combine, blind rate decision) in is95.py, GSM channel decoding (burst de-interleavers, Fire code, TCH/FS frames, two receivers) in gsm.py.  codes.py / synth.py hold constants and synthetic-input generation for the measurement.
 """
 from .codes import COMMON_CODES, Code, DecoderConfig, get_decoding_config, SOFT16, SOFT8, HARD8  # noqa: F401
 from .decoder import (BatchDecoder, DecodePipeline, ViterbiBranchTable, ViterbiDecoder_Config, ViterbiDecoder_Core,  # noqa: F401
@@ -28,9 +28,14 @@ from .dvbt import (DVBT_MODES, DVBT_RATES, DvbtDecoder, DvbtMode, dvbt_deinterle
                    dvbt_steps_per_symbol, dvbt_symbol_permutation)
 from .is95 import (IS95_CRC8, IS95_CRC12, IS95_POLYNOMIALS, IS95_RATE_SET_1, Is95Rate, Is95TrafficDecoder, is95_deinterleave_numpy,  # noqa: F401
                    is95_permutation, is95_rate_decide_numpy, is95_traffic_frame_numpy)
-from . import _lib, crc, dab, dabplus, dist, dvb, dvbt, frame_sync, is95, lte, reed_solomon, sync, synth, wifi  # noqa: F401
+from .gsm import (GSM_BLOCK, GSM_DIAGONAL, GSM_POLYNOMIALS, GSM_RACH_CRC6, GSM_SCH_CRC10, GSM_TCHFS_CRC3, GsmControlDecoder, GsmTchfDecoder,  # noqa: F401
+                  gsm_deinterleave_numpy, gsm_facch_steal_numpy, gsm_fire_encode_numpy, gsm_fire_numpy, gsm_interleave_map, gsm_tchfs_bursts_numpy,
+                  gsm_tchfs_class1_numpy, gsm_tchfs_numpy, gsm_xcch_bursts_numpy)
+from . import _lib, crc, dab, dabplus, dist, dvb, dvbt, frame_sync, gsm, is95, lte, reed_solomon, sync, synth, wifi  # noqa: F401
 
-__all__ = ["IS95_CRC8", "IS95_CRC12", "IS95_POLYNOMIALS", "IS95_RATE_SET_1", "Is95Rate", "Is95TrafficDecoder", "is95_deinterleave_numpy", "is95_permutation",
+__all__ = ["GSM_BLOCK", "GSM_DIAGONAL", "GSM_POLYNOMIALS", "GSM_RACH_CRC6", "GSM_SCH_CRC10", "GSM_TCHFS_CRC3", "GsmControlDecoder", "GsmTchfDecoder",
+           "gsm_deinterleave_numpy", "gsm_facch_steal_numpy", "gsm_fire_encode_numpy", "gsm_fire_numpy", "gsm_interleave_map", "gsm_tchfs_bursts_numpy",
+           "gsm_tchfs_class1_numpy", "gsm_tchfs_numpy", "gsm_xcch_bursts_numpy", "IS95_CRC8", "IS95_CRC12", "IS95_POLYNOMIALS", "IS95_RATE_SET_1", "Is95Rate", "Is95TrafficDecoder", "is95_deinterleave_numpy", "is95_permutation",
            "is95_rate_decide_numpy", "is95_traffic_frame_numpy", "DVBT_MODES", "DVBT_RATES", "DvbtDecoder", "DvbtMode", "dvbt_deinterleave_numpy", "dvbt_interleave_numpy", "dvbt_puncture_numpy",
            "dvbt_steps_per_symbol", "dvbt_symbol_permutation", "WIFI_POLYNOMIALS", "WIFI_RATES", "WifiDecoder", "WifiRate", "wifi_deinterleave_numpy", "wifi_descramble_numpy", "wifi_interleave_map",
            "wifi_ppdu_numpy", "wifi_scrambler_numpy", "wifi_signal_field_numpy", "wifi_signal_parse_numpy", "WIFI_FCS", "DABPLUS_RS_120_110", "FIRECODE", "DabPlusDecoder", "dabplus_au_table_numpy", "dabplus_lock_numpy", "dabplus_superframe_numpy",

@@ -279,3 +279,33 @@ def is95_counted(symbols, bytes, errors, compared, dtype, frames):
             if dense(x, torch.int32, frames, f"{what}[{h}]").data_ptr() in seen and frames:
                 raise ValueError("the count tensors must be distinct")
             seen.add(x.data_ptr())
+
+
+def gsm_bursts(x, dtype):
+    """(rows, bursts, row stride, burst stride), in elements, of a gsm_deinterleave call: the rule of soft_frames with 116 elements a
+    burst, [rows][bursts][>= 116] or [bursts][...] (one row), bursts a multiple of 4"""
+    rows, bursts, rs, bs = soft_frames(x, dtype, "bursts", 116)
+    if bursts % 4:
+        raise ValueError("bursts must hold a multiple of 4 bursts a row")
+    return rows, bursts, rs, bs
+
+
+def gsm_outputs(out, dtype, rows, blocks, diagonal):
+    """the outputs of a gsm_deinterleave call, a dict: full, class1, class2 dense tensors of `dtype` with rows * blocks * 456 / 378 / 78
+    elements, steal dense int32 [rows * blocks] -- not all four absent --, n_out int32 [rows]; in diagonal mode hist_out, dense of `dtype`
+    with rows * 464 elements, together with fill_out, int32 [rows]; in block mode neither.  returns the seven in the ABI's order, None
+    where absent"""
+    import torch
+    names = ("hist_out", "fill_out", "n_out", "full", "class1", "class2", "steal")
+    if set(out) - set(names):
+        raise ValueError(f"out may hold {names}")
+    got = [out.get(k) for k in names]
+    if all(x is None for x in got[3:]):
+        raise ValueError("out must hold one of full, class1, class2, steal")
+    if (got[0] is None) != (got[1] is None) or (not diagonal and got[0] is not None):
+        raise ValueError("hist_out and fill_out come together, in diagonal mode only")
+    for x, dt, n, k in zip(got, (dtype, torch.int32, torch.int32, dtype, dtype, dtype, torch.int32),
+                           (rows * 464, rows, rows, rows * blocks * 456, rows * blocks * 378, rows * blocks * 78, rows * blocks), names):
+        if x is not None:
+            dense(x, dt, n, f"out[{k!r}]")
+    return got

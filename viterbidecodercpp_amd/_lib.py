@@ -47,6 +47,7 @@ EXPORTS = [
     "vit_hip_wifi_deinterleave_batch", "vit_hip_wifi_signal_batch", "vit_hip_wifi_data_batch",
     "vit_hip_dvbt_deinterleave_batch",
     "vit_hip_is95_deinterleave_batch", "vit_hip_is95_channel_errors_batch", "vit_hip_is95_rate_decide_batch",
+    "vit_hip_gsm_deinterleave_batch", "vit_hip_gsm_fire_batch", "vit_hip_gsm_tchfs_batch",
 ]
 
 
@@ -87,6 +88,7 @@ ENCODE_TAIL, ENCODE_TAIL_BITING = 1, 2
 SYNC_SWAP_PAIRS, SYNC_NEGATE_EVEN, SYNC_NEGATE_ODD = 1, 2, 4
 SYNC_MAX_HYPOTHESES = 64
 MARKER_ACCUMULATE = 1
+GSM_BLOCK, GSM_DIAGONAL, GSM_NEGATE, GSM_LSB_FIRST = 0, 1, 1, 1
 
 
 class VitHipSyncHypothesis(C.Structure):
@@ -197,6 +199,9 @@ def load():
     L.vit_hip_is95_channel_errors_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(vp), C.POINTER(vp), vp]
     L.vit_hip_is95_rate_decide_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), sz,
                                                  C.POINTER(C.c_uint32), C.c_uint32, vp, vp, sz, vp]
+    L.vit_hip_gsm_deinterleave_batch.argtypes = [vp, vp, sz, sz, sz, sz, C.c_uint, C.c_uint, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.vit_hip_gsm_fire_batch.argtypes = [vp, vp, sz, sz, C.c_uint, C.c_uint, vp, vp, sz, vp]
+    L.vit_hip_gsm_tchfs_batch.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp]
     L.vit_hip_broadcast_table.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
     L.vit_hip_synth_batch.argtypes = [vp, sz, sz, C.c_uint64, C.c_uint64, C.c_float, i32, vp, vp, vp]
     L.vit_hip_count_bit_errors.argtypes = [vp, vp, vp, sz, vp, vp]

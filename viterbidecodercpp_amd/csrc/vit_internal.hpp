@@ -33,6 +33,8 @@
 //                    of the stream decode (kernels_dvbt.hpp); behind the decode DVB-T is the DVB-S chain of vit_dvb.hip
 //   vit_is95.hip     the IS-95A forward traffic channel around the K = 9 decode: descrambling, block de-interleaver and the combining of
 //                    the repetitions under the four rate hypotheses in front, the blind rate decision behind (kernels_is95.hpp)
+//   vit_gsm.hip      GSM channel decoding around the K = 5 decode: the block and diagonal burst de-interleavers in front, the Fire code
+//                    of the control channels and the TCH/FS frame behind (kernels_gsm.hpp)
 // arg_rules.hpp states what every unit's argument rule is worded in: overlap, extent, misaligned.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -838,6 +838,97 @@ class BatchDecoder(_OuterChain):
             (C.c_uint32 * 4)(*num), int(ser_den), _ptr(decision), _ptr(info), istride, self._stream()))
         return decision, info
 
+    def gsm_deinterleave(self, bursts, mode, negate: bool = False, hist=None, fill=None, out=None,
+                         want=("full", "class1", "class2", "steal")):
+        """the GSM burst de-interleaver in front of decode (vit_hip_gsm_deinterleave_batch; 3GPP TS 45.003).  bursts: a CUDA tensor of the
+        decoder's symbol dtype [rows][4 m][>= 116] (or [4 m][...]: one row), e(B, 0 .. 115) with the stealing flags at 57 and 58; a view
+        with larger strides is read in place.  mode gsm.GSM_BLOCK (control channels: 4 bursts a block, no history) or gsm.GSM_DIAGONAL
+        (TCH/F, FACCH/F: 8 bursts a block with half-block overlap; hist / fill: the hist_out [rows][464] and fill_out int32 [rows] the
+        call before returned, None: no history, and a row gives m - 1 blocks).  negate: every value negated on the way, clamped to the
+        dtype.  returns a dict: full [rows][m][228][2] (decode reads it with L = 224), class1 [rows][m][189][2] (L = 185), class2
+        [rows][m][78], steal int32 [rows][m] (the sum of the block's stealing flags), n_out int32 [rows] (the blocks the row gave; the
+        slots behind them are zeros) and, in diagonal mode, hist_out, fill_out; `want` names which of the first four are allocated, out
+        = a dict of such tensors is written in place and nothing else.  The rule on the host: gsm.gsm_deinterleave_numpy.  A decoder of
+        rate 1/2 only.  Nothing is copied to the host."""
+        from . import gsm
+        t = self.torch
+        mode = gsm._mode(mode)
+        if self.R != 2:
+            raise ValueError("the GSM burst de-interleaver feeds a rate 1/2 decoder")
+        rows, n_bursts, rs, bs = _args.gsm_bursts(bursts, self._soft_dtype)
+        m = n_bursts // 4
+        if mode == gsm.GSM_BLOCK and (hist is not None or fill is not None):
+            raise ValueError("the block mode carries no history")
+        if (hist is None) != (fill is None):
+            raise ValueError("hist and fill come together")
+        if hist is not None:
+            _args.dense(hist, self._soft_dtype, rows * 464, "hist"), _args.dense(fill, t.int32, rows, "fill")
+        if out is None:
+            shapes = {"full": (rows, m, 228, 2), "class1": (rows, m, 189, 2), "class2": (rows, m, 78)}
+            out = {k: self._empty((rows, m), t.int32) if k == "steal" else self._empty(shapes[k], self._soft_dtype) for k in want}
+            out["n_out"] = self._empty((rows,), t.int32)
+            if mode == gsm.GSM_DIAGONAL:
+                out["hist_out"], out["fill_out"] = self._empty((rows, 464), self._soft_dtype), self._empty((rows,), t.int32)
+        got = _args.gsm_outputs(out, self._soft_dtype, rows, m, mode == gsm.GSM_DIAGONAL)
+        result = dict(zip(("hist_out", "fill_out", "n_out", "full", "class1", "class2", "steal"), got))
+        if rows == 0 or m == 0:
+            return result
+        _lib.check(_lib.load().vit_hip_gsm_deinterleave_batch(self._handle._h, _ptr(bursts), rs, bs, rows, n_bursts, mode,
+                                                              _lib.GSM_NEGATE if negate else 0, _ptr(hist), _ptr(fill), *[_ptr(x) for x in got],
+                                                              self._stream()))
+        return result
+
+    def gsm_fire(self, bytes, max_burst: int = 12, lsb_first: bool = False, out=None):
+        """the Fire code of the GSM control channels (vit_hip_gsm_fire_batch): bytes, uint8 CUDA [frames][>= 28] with contiguous rows, what
+        decode returns with L = 224 -- 184 data bits, 40 parity bits.  A frame whose syndrome is not 0 is searched for the one error burst
+        of at most max_burst (0 .. 12; 0: detect only) bits that explains it, and that burst is flipped.  returns (status int32 [frames][4]
+        = (status, first_bit, syndrome_lo, syndrome_hi): status 0 clean, 1 .. 12 the length of the corrected burst from bit first_bit on,
+        -1 not correctable; data uint8 [frames][23], MSB-first or, with lsb_first, d(8 i + b) as bit b of byte i).  out = (status, data)
+        reuses those tensors; data rows may be wider, and data may be `bytes` itself: in place.  The rule on the host:
+        gsm.gsm_fire_numpy.  Nothing is copied to the host."""
+        t = self.torch
+        max_burst = int(max_burst)
+        if not 0 <= max_burst <= 12:
+            raise ValueError("max_burst must be 0 .. 12")
+        frames, stride = _args.wifi_rows(bytes, t.uint8, 28, "bytes")
+        if out is None:
+            out = (self._empty((frames, 4), t.int32), self._empty((frames, 23), t.uint8))
+        status, data = out
+        _args.dense(status, t.int32, frames * 4, "out[0]")
+        dframes, dstride = _args.wifi_rows(data, t.uint8, 23, "out[1]")
+        if dframes != frames:
+            raise ValueError(f"out[1] must hold [{frames}] rows")
+        if data.data_ptr() == bytes.data_ptr() and frames == 1:
+            dstride = stride
+        if frames == 0:
+            return status, data
+        _lib.check(_lib.load().vit_hip_gsm_fire_batch(self._handle._h, _ptr(bytes), stride, frames, max_burst,
+                                                      _lib.GSM_LSB_FIRST if lsb_first else 0, _ptr(status), _ptr(data), dstride, self._stream()))
+        return status, data
+
+    def gsm_tchfs(self, bytes, class2, out=None):
+        """the GSM TCH/FS frame behind decode (vit_hip_gsm_tchfs_batch): bytes, uint8 CUDA [frames][>= 24] with contiguous rows, what decode
+        returns with L = 185 for the class1 output of gsm_deinterleave, and class2, its class2 output as [frames][78].  returns (speech
+        uint8 [frames][33]: the 260 bits MSB-first -- class I reordered, class II by hard decision against the decoder's
+        soft_decision_high / low --, the last four bits 0; status int32 [frames][2] = (parity_syndrome: 0 where the 3 parity bits over the
+        first 50 bits hold, class2_erasures: class II values at the midpoint)).  out = (speech, status) reuses those tensors; speech rows
+        may be wider.  The rule on the host: gsm.gsm_tchfs_numpy.  Nothing is copied to the host."""
+        t = self.torch
+        frames, stride = _args.wifi_rows(bytes, t.uint8, 24, "bytes")
+        _args.dense(class2, self._soft_dtype, frames * 78, "class2")
+        if out is None:
+            out = (self._empty((frames, 33), t.uint8), self._empty((frames, 2), t.int32))
+        speech, status = out
+        sframes, sstride = _args.wifi_rows(speech, t.uint8, 33, "out[0]")
+        if sframes != frames:
+            raise ValueError(f"out[0] must hold [{frames}] rows")
+        _args.dense(status, t.int32, frames * 2, "out[1]")
+        if frames == 0:
+            return speech, status
+        _lib.check(_lib.load().vit_hip_gsm_tchfs_batch(self._handle._h, _ptr(bytes), stride, _ptr(class2), frames, _ptr(speech), sstride,
+                                                       _ptr(status), self._stream()))
+        return speech, status
+
     def dab_deinterleave(self, frames, n_frames=None, source_index=None, hist=None, fill=None, n_received: int = None, out=None):
         """the DAB time de-interleaver fused with depuncturing, in front of decode (vit_hip_dab_deinterleave_batch; ETSI EN 300 401
         clauses 12 and 11).  frames: the received soft bits, a CUDA tensor of the decoder's symbol dtype [rows][max_frames][>= n] (or
